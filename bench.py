@@ -2,12 +2,19 @@
 """bench.py — macroblocks/s of the MI355X reconstruction path on BASELINE.json's workload.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: starts its own N ranks, launch_ranks below)
+    python bench.py --gpus 1 --steps K --warmup W --dump-outputs DIR      (also writes DIR/recon.npy, dump_outputs below)
+    python bench.py --gpus 1 --steps K --warmup W --full   (also: oracle check, CPU baseline, queue lanes, the 4K line)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 A "step" is one pass of the hot path over one batch of synthetic input: every rank reconstructs its
 300-frame shard of the 1080p all-intra workload (BASELINE.json configs[1]; N GPUs = configs[3]'s
 300 frames per GPU, weak scaling) with inputs already resident in HBM. Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps and prints the line. Everything else the benchmark measures or checks
+runs only with --full: the bit-exact comparison with the oracle and the shard checksums, the CPU baseline, the
+`pipelined` object (queue lanes) and the secondary 4K line; --no-verify, --no-cpu-baseline, --no-pipelined and
+--no-secondary then switch single parts off again as before.
 """
 import argparse
 import json
@@ -91,6 +98,48 @@ ALG_BYTES_PER_MB = 1168          # 768 B coefficients + 16 B record read, 384 B 
 HBM_PEAK_GBS = 8000.0            # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 
 
+DUMP_MAX_VALUES = 8 << 20        # float32 values per dumped array (32 MB)
+
+
+def generate_shard(fp, cfg, cid, first, n_frames):
+    """synth.generate over the shard, one block of frames per host thread (ctypes releases the GIL). Every frame's
+    generator is seeded by its own index (synth.py), so the arrays are exactly those of a single call."""
+    from concurrent.futures import ThreadPoolExecutor
+    from dryv_amd import abi, shard, synth
+    per = fp.pic_width_in_mbs * fp.pic_height_in_mbs
+    mbs = np.empty(n_frames * per, dtype=abi.MB_DESC_DTYPE)
+    coeffs = np.empty((n_frames * per, abi.COEFFS_PER_MB), dtype=np.int16)
+    workers = max(1, min(16, len(os.sched_getaffinity(0)), n_frames))
+    synth._load()   # (once, before the threads would race to do it)
+
+    def one(block):
+        a, n = block
+        synth.generate(fp, cfg, cid, first + a, n, mbs[a * per:(a + n) * per], coeffs[a * per:(a + n) * per])
+    with ThreadPoolExecutor(workers) as ex:
+        list(ex.map(one, shard.partition_frames(n_frames, workers)))
+    return mbs, coeffs
+
+
+def dump_rows(n_mbs):
+    """The 384-byte runs of an output buffer of n_mbs macroblocks that --dump-outputs writes: all of them (None) up to
+    DUMP_MAX_VALUES bytes, above that a fixed, seeded choice in ascending order."""
+    k = DUMP_MAX_VALUES // 384
+    if n_mbs <= k:
+        return None
+    return np.sort(np.random.default_rng(0x64727976).choice(n_mbs, size=k, replace=False))
+
+
+def dump_outputs(path, d_out, n_mbs):
+    """--dump-outputs: what the timed path left in its output buffer after the last timed step (the reconstructed
+    4:2:0 pixels, 384 bytes per macroblock), as float32[rows, 384]: the same rows in every run with the same arguments."""
+    import torch
+    planes, rows = d_out.view(n_mbs, 384), dump_rows(n_mbs)
+    if rows is not None:
+        planes = planes[torch.from_numpy(rows).to(d_out.device)]
+    os.makedirs(os.path.dirname(path) or ".", exist_ok=True)
+    np.save(path, planes.cpu().numpy().astype(np.float32))
+
+
 def cpu_baseline(fp, mbs, coeffs, n_frames, gpu_out, frame_bytes, sample_frames):
     """Times the oracle (the bit-exact port of the reference's Rust path) on one host core over the
     first `sample_frames` frames of the same workload, and uses the same run to verify the GPU output."""
@@ -140,7 +189,7 @@ def secondary_line(name, device, dev_index, steps, warmup, cpu_frames):
     cid, w, h, frames, t8, kw = synth.WORKLOADS[name]
     fp = dryv_amd.make_frame_params(w, h, transform_8x8=t8)
     per = w * h
-    mbs, coeffs = synth.generate(fp, synth.config(**kw), cid, 0, frames)
+    mbs, coeffs = generate_shard(fp, synth.config(**kw), cid, 0, frames)
     d_mbs = torch.from_numpy(mbs.view(np.uint8).reshape(-1)).to(device)
     d_coeffs = torch.from_numpy(coeffs).to(device)
     d_out = torch.zeros(frames * per * 384, dtype=torch.uint8, device=device)
@@ -214,7 +263,8 @@ def pipelined_line(ctx, fp, n_frames, d_mbs, d_coeffs, d_out, n_mbs, steps, warm
         dist.barrier()
     elapsed = time.perf_counter() - t0
     ctx.set_queue_lanes(1)
-    same = all(shard.plane_checksum(o) == want for o in outs)
+    # (a run of fewer steps than lanes leaves the last lanes' buffers unwritten: only what a launch wrote is compared)
+    same = all(shard.plane_checksum(o) == want for o in outs[:max(1, min(lanes, max(steps, warmup)))])
     if world > 1:
         t = torch.tensor([elapsed, 0.0 if same else 1.0], dtype=torch.float64, device=ctrl)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -289,10 +339,16 @@ def main():
                     help="skip the `pipelined` object (the same workload over the library's queue lanes) of a single-GPU run")
     ap.add_argument("--no-secondary", action="store_true",
                     help="skip the secondary line (C3: 4K, 8x8 transform) that the default single-GPU C2 run also measures")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also check the output against the oracle and measure the CPU baseline, the "
+                         "`pipelined` object and the secondary line (a plain run only times the steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the output buffer of the last timed step to DIR/recon.npy (float32; N ranks: recon_rank<r>.npy)")
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / control-plane rehearsal without a GPU: ranks over gloo, no reconstruction, value null")
     args = ap.parse_args()
-
+    if not args.full:
+        args.no_verify = args.no_cpu_baseline = args.no_pipelined = args.no_secondary = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -329,7 +385,7 @@ def main():
     frame_bytes = per * 384
 
     # ---- synthetic shard, generated on the host and made resident in HBM ------------------------
-    mbs, coeffs = synth.generate(fp, synth.config(**kw), cid, first, n_frames)
+    mbs, coeffs = generate_shard(fp, synth.config(**kw), cid, first, n_frames)
     d_mbs = torch.from_numpy(mbs.view(np.uint8).reshape(-1)).to(device)
     d_coeffs = torch.from_numpy(coeffs).to(device)
     d_out = torch.zeros(n_mbs * 384, dtype=torch.uint8, device=device)
@@ -381,6 +437,8 @@ def main():
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     elapsed = float(t.item())
+    if args.dump_outputs:
+        dump_outputs(os.path.join(args.dump_outputs, "recon.npy" if world == 1 else "recon_rank%d.npy" % rank), d_out, n_mbs)
 
     # ---- every rank checks its own shard against the oracle after the timed region: the first and the last frame
     # of the shard (bit-exact), then the per-rank verdicts, checksums and kernel times are gathered
@@ -391,7 +449,7 @@ def main():
             st, want = oracle.reconstruct(fp, 1, mbs[fidx * per:(fidx + 1) * per], coeffs[fidx * per:(fidx + 1) * per])
             got = d_out[fidx * frame_bytes:(fidx + 1) * frame_bytes].cpu().numpy()
             verified = verified and st == 0 and bool(np.array_equal(got, want))
-    reports = shard.gather_reports(n_frames, n_mbs, shard.plane_checksum(d_out), ctrl, world)
+    reports = shard.gather_reports(n_frames, n_mbs, shard.plane_checksum(d_out) if args.full else 0, ctrl, world)
     total_mbs = sum(r[1] for r in reports)
     vt = torch.tensor([1.0 if verified else 0.0, float(np.mean(kernel_ms))], dtype=torch.float64, device=ctrl)
     if world > 1:
@@ -453,7 +511,7 @@ def main():
                        "kernel_ms_per_rank": {"min": kernel_ms_min, "max": kernel_ms_max},
                        "steps_queued_on_stream": not args.sync_each_step,
                        "shards_verified_bit_exact": (world if not args.no_verify else 0),
-                       "shard_checksums": ["%016x" % (r[2] & 0xFFFFFFFFFFFFFFFF) for r in reports]},
+                       "shard_checksums": ["%016x" % (r[2] & 0xFFFFFFFFFFFFFFFF) for r in reports] if args.full else None},
             # frac: the contract's figure (algorithmic bytes of this rank's launch / the kernel's average duration by HIP events);
             # frac_wall: the same bytes / this job's wall time per step (what `value` is made of: it also pays for the
             # workspace reset in front of every launch and for whatever the queue leaves between launches)

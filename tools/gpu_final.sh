@@ -5,11 +5,11 @@ set -o pipefail
 O=gpurun_out/final; mkdir -p $O
 timeout -k 10 900 python -m pytest tests -m gpu -x -q --timeout 300 > $O/pytest.log 2>&1; rc=$?; echo "pytest rc=$rc"; tail -3 $O/pytest.log
 [ $rc -eq 0 ] || exit 1
-timeout -k 10 400 python bench.py > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
+timeout -k 10 400 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err || { echo "bench failed"; tail -5 $O/bench_default.err; exit 1; }
 echo "bench ok"
-timeout -k 10 600 python bench.py --workload C3_4k_intra_8x8 --steps 20 --warmup 5 > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench c3 failed"; tail -5 $O/bench_c3.err; exit 1; }
+timeout -k 10 600 python bench.py --workload C3_4k_intra_8x8 --steps 20 --warmup 5 --full > $O/bench_c3.json 2> $O/bench_c3.err || { echo "bench c3 failed"; tail -5 $O/bench_c3.err; exit 1; }
 echo "bench c3 ok"
-DRYV_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 10 --warmup 3 2> $O/bench_2ranks.err | grep '^{' > $O/bench_2ranks_gloo_one_gpu.json || { echo "2-rank rehearsal failed"; tail -5 $O/bench_2ranks.err; exit 1; }
+DRYV_BENCH_BACKEND=gloo timeout -k 10 400 python bench.py --gpus 2 --steps 10 --warmup 3 --full 2> $O/bench_2ranks.err | grep '^{' > $O/bench_2ranks_gloo_one_gpu.json || { echo "2-rank rehearsal failed"; tail -5 $O/bench_2ranks.err; exit 1; }
 echo "2-rank launcher rehearsal ok"
 timeout -k 10 600 bash tools/profile_round.sh r04_c2 > $O/profile_c2.log 2>&1 || { echo "profile c2 failed"; tail -5 $O/profile_c2.log; exit 1; }
 echo "profile c2 ok"
