@@ -5,6 +5,6 @@ include/dryv_recon.h), the host-side mirror of the reference's `Frame` interface
 host/frame.hpp) and the synthetic batch generator used to exercise it (synth.py).
 """
 from .abi import (DRYV_OK, DRYV_E_INVALID, DRYV_E_UNSUPPORTED, DRYV_E_DEVICE, DRYV_E_NOMEM,  # noqa: F401
-                  DRYV_E_STATE, DRYV_E_NODEVICE, FrameParams, MbDesc, MB_DESC_DTYPE, COEFFS_PER_MB,
+                  DRYV_E_STATE, DRYV_E_NODEVICE, FrameParams, MbDesc, MB_DESC_DTYPE, COEFFS_PER_MB, InterMb, INTER_MB_DTYPE,
                   load_library, make_frame_params, strerror)
-from .frame import Frame, ReconContext, ReconError  # noqa: F401
+from .frame import Frame, InterContext, ReconContext, ReconError  # noqa: F401

@@ -48,10 +48,19 @@ def build_recon(force=False):
                                                    "deblock_params.h", "deblock_launch.h",
                                                    "kparams.h", "recon_params.h")] + [
                    os.path.join(HERE, "..", "include", "dryv_recon.h")]
+    # the inter prediction stage: objects of their own, compiled without packed-fp32 instruction selection, linked into
+    # the same library (the other sources' command line is what bench.py's numbers were measured with: unchanged)
+    inter_srcs = [os.path.join(CSRC, f) for f in ("inter.hip", "inter_api.hip")]
+    deps += inter_srcs + [os.path.join(CSRC, f) for f in ("inter_kernel.h", "inter_launch.h", "inter_params.h")]
     os.makedirs(LIB, exist_ok=True)
     if force or _stale(RECON_SO, deps):
+        objs = []
+        for s in inter_srcs:
+            objs.append(os.path.join(LIB, os.path.basename(s)[:-4] + ".o"))
+            _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Xclang", "-target-feature", "-Xclang",
+                  "-packed-fp32-ops", "-c", "-o", objs[-1], s])
         _run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-              "-o", RECON_SO] + srcs)
+              "-o", RECON_SO] + srcs + ["-x", "none"] + objs)
     return RECON_SO
 
 

@@ -87,6 +87,18 @@ MB_DESC_DTYPE = np.dtype([
 ])
 assert MB_DESC_DTYPE.itemsize == 16 and C.sizeof(MbDesc) == 16 and C.sizeof(FrameParams) == 496
 
+
+class InterMb(C.Structure):
+    """dryv_inter_mb (80 bytes): one P macroblock of the inter prediction stage."""
+    _fields_ = [("mb_type", C.c_uint8), ("qp", C.c_uint8), ("flags", C.c_uint8), ("reserved0", C.c_uint8),
+                ("ref_idx", C.c_int8 * 4), ("reserved", C.c_uint8 * 8), ("mv", (C.c_int16 * 2) * 16)]
+
+
+INTER_TRANSFORM_8X8, INTER_NO_RESIDUAL = 1, 2   # dryv_inter_mb.flags
+INTER_MB_DTYPE = np.dtype([("mb_type", "u1"), ("qp", "u1"), ("flags", "u1"), ("reserved0", "u1"), ("ref_idx", "i1", (4,)),
+                           ("reserved", "u1", (8,)), ("mv", "<i2", (16, 2))])
+assert INTER_MB_DTYPE.itemsize == 80 and C.sizeof(InterMb) == 80 and InterMb.mv.offset == 16
+
 # every function include/dryv_recon.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dryv_recon_frame_bytes": (C.c_size_t, [C.POINTER(FrameParams)]),
@@ -117,6 +129,13 @@ SYMBOLS = {
                                             C.c_void_p]),
     "dryv_recon_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dryv_recon_stream": (C.c_void_p, [C.c_void_p]),
+    "dryv_inter_check": (C.c_int, [C.POINTER(FrameParams), C.c_uint32, C.c_uint32]),
+    "dryv_inter_create": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, C.c_void_p]),
+    "dryv_inter_destroy": (None, [C.c_void_p]),
+    "dryv_inter_submit_device": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dryv_inter_sync": (C.c_int, [C.c_void_p]),
+    "dryv_inter_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dryv_recon_strerror": (C.c_char_p, [C.c_int]),
     "dryv_recon_last_device_error": (C.c_char_p, [C.c_void_p]),
     "dryv_recon_abi_version": (C.c_int, []),

@@ -203,6 +203,57 @@ class ReconContext:
         return self._lib.dryv_recon_stream(self._h)
 
 
+class InterContext:
+    """One dryv_inter_ctx: the inter prediction stage (P macroblocks, H.264 8.4.2.2 + residual) on `device`, on a stream of
+    its own or on a borrowed one (`stream`: a raw hipStream_t, e.g. ReconContext.stream: the stage then runs behind
+    reconstruction on that stream). Not thread-safe."""
+
+    def __init__(self, device=0, stream=None):
+        self._lib = abi.load_library()
+        h = C.c_void_p()
+        _check(self._lib.dryv_inter_create(C.byref(h), int(device), C.c_void_p(stream)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.dryv_inter_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.close()
+
+    def submit_device(self, fp, n_frames, refs, d_mbs, d_coeffs, d_yuv_out):
+        """refs: n_frames sequences of n_refs raw device pointers (reference pictures in the output layout); the other three
+        are raw device pointers: abi.INTER_MB_DTYPE records, int16 (n_mbs, 384), the output pictures. Completes at sync()."""
+        flat = [int(p) for per_frame in refs for p in per_frame]
+        n_refs = len(flat) // int(n_frames) if n_frames else 0
+        if n_refs * int(n_frames) != len(flat) or any(len(r) != n_refs for r in refs):
+            raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
+        tab = (C.c_void_p * max(len(flat), 1))(*flat)
+        _check(self._lib.dryv_inter_submit_device(self._h, C.byref(fp), int(n_frames), n_refs, tab, C.c_void_p(d_mbs),
+                                                  C.c_void_p(d_coeffs), C.c_void_p(d_yuv_out)))
+
+    def sync(self, allow_unsupported=False):
+        st = self._lib.dryv_inter_sync(self._h)
+        if not (allow_unsupported and st == abi.DRYV_E_UNSUPPORTED):
+            _check(st)
+        return st
+
+    def last_kernel_ms(self):
+        ms = C.c_float()
+        _check(self._lib.dryv_inter_last_kernel_ms(self._h, C.byref(ms)))
+        return float(ms.value)
+
+
 class Frame:
     """Mirror of the reference's `Frame` for one picture (one slice NAL, decoder.rs:124)."""
 

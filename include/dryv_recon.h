@@ -215,6 +215,57 @@ int dryv_recon_wide_rerun_stats(dryv_recon_ctx *ctx, int *events, int *batches);
  * their own work or record their own events against it. */
 void *dryv_recon_stream(dryv_recon_ctx *ctx);
 
+/* ---- inter prediction stage: motion-compensated reconstruction of P macroblocks --------------------------------------------
+ * ITU-T H.264 clauses 8.4.2.2 (fractional sample interpolation, default unweighted prediction) and 8.5.8 - 8.5.13 (residual) for
+ * P macroblocks of frame pictures, 4:2:0, 8 bit, one reference list. dryv has no inter prediction (README.md:12 unchecked, the
+ * macroblock loop's todo!() at frame/mod.rs:88): there is no reference behaviour to be equal to; this stage follows the
+ * standard itself. A stage object of its own, next to dryv_recon_ctx.
+ *
+ * Not done here, by the caller instead: motion-vector prediction and P_Skip inference (records carry final vectors; a skipped
+ * macroblock is one vector on all 16 blocks plus flag bit1). Not supported: B slices, bi-prediction, explicit weighted
+ * prediction, field / MBAFF, intra macroblocks inside P pictures (mb_type != 0: status bit, DRYV_E_UNSUPPORTED at sync, the
+ * macroblock zero-filled), deblocking of inter edges.
+ *
+ * Reference pictures: each a full coded picture in this library's own output layout (dryv_recon_frame_bytes), 16-byte aligned.
+ * Vectors may point anywhere; samples outside the picture are the nearest edge sample (8.4.2.2's coordinate clipping). An
+ * output picture of a call must not be one of that call's references.
+ * Coefficients: int16[384] per macroblock in the slot layout above: luma as 16 lists of 16 (4x4 blocks in figure 6-10 order), or
+ * 4 lists of 64 with flag bit0; then Cb and Cr, each DC[4] + 4 x AC[15].
+ * Scaling lists: the standard's INTER lists of the dryv_frame_params: 4x4 lists 3 / 4 / 5 for Y / Cb / Cr, 8x8 list 1. (The intra
+ * path's use of list 0 for every plane is a quirk of dryv, SURVEY.md Q3, and does not carry over.)
+ * Arithmetic: 32 bit. Exact whenever every value of 8.5.12 - 8.5.13 fits int32, which covers every conformant stream (the
+ * standard bounds them to 16 bits); beyond that the result is int32 wrap-around, unflagged: unlike the intra path there is no
+ * 64-bit re-run. */
+typedef struct dryv_inter_mb { /* 80 bytes, raster order, frames concatenated */
+  uint8_t mb_type;             /* 0 = P (inter). Anything else: unsupported, zero-filled */
+  uint8_t qp;                  /* QPY 0..51 (above: unsupported) */
+  uint8_t flags;               /* bit0 transform_size_8x8_flag; bit1 no residual: the macroblock's coefficient slot is NOT read */
+  uint8_t reserved0;
+  int8_t ref_idx[4];           /* per 8x8 quadrant (figure 6-10 order), 0..n_refs-1 (outside: unsupported, the table is not read) */
+  uint8_t reserved[8];
+  int16_t mv[16][2];           /* per 4x4 block, figure 6-10 order (the order of the coefficient lists), (x, y) in quarter luma samples */
+} dryv_inter_mb;
+
+typedef struct dryv_inter_ctx dryv_inter_ctx;
+/* dryv_recon_check_params plus 1 <= n_refs <= 16 (DRYV_E_INVALID otherwise); no device needed. */
+int dryv_inter_check(const dryv_frame_params *fp, uint32_t n_frames, uint32_t n_refs);
+/* stream: a hipStream_t to borrow (dryv_recon_stream(ctx): the stage then runs behind reconstruction on that stream), or NULL:
+ * a stream of the stage's own. DRYV_E_NODEVICE without a GPU. */
+int dryv_inter_create(dryv_inter_ctx **out, int device_ordinal, void *stream);
+void dryv_inter_destroy(dryv_inter_ctx *ctx);
+/* Predicts and reconstructs n_frames P pictures into d_yuv_out. d_refs is a HOST array [n_frames][n_refs] of device pointers
+ * (copied before the call returns); d_mbs (dryv_inter_mb records), d_coeffs and d_yuv_out are device pointers; all three and
+ * every reference 16-byte aligned (DRYV_E_INVALID otherwise). Asynchronous on the stage's stream; pair with dryv_inter_sync.
+ * May be called again before the sync: the calls run in order. On a borrowed stream the same rule holds as for every other
+ * consumer: a reconstructed batch is final only after its own dryv_recon_sync (which may run a flagged batch again). */
+int dryv_inter_submit_device(dryv_inter_ctx *ctx, const dryv_frame_params *fp, uint32_t n_frames, uint32_t n_refs,
+                             const void *const *d_refs, const void *d_mbs, const void *d_coeffs, void *d_yuv_out);
+/* Waits for everything submitted: DRYV_OK, DRYV_E_UNSUPPORTED (a record with mb_type != 0, qp > 51 or a ref_idx outside
+ * 0..n_refs-1 since the last sync: those macroblocks are zero-filled, the others are reconstructed) or DRYV_E_DEVICE. */
+int dryv_inter_sync(dryv_inter_ctx *ctx);
+/* Device time of the most recent launch (the dispatch's own start and end). Valid after dryv_inter_sync. */
+int dryv_inter_last_kernel_ms(dryv_inter_ctx *ctx, float *ms);
+
 const char *dryv_recon_strerror(int status);
 const char *dryv_recon_last_device_error(dryv_recon_ctx *ctx);
 int dryv_recon_abi_version(void);
