@@ -99,6 +99,32 @@ INTER_MB_DTYPE = np.dtype([("mb_type", "u1"), ("qp", "u1"), ("flags", "u1"), ("r
                            ("reserved", "u1", (8,)), ("mv", "<i2", (16, 2))])
 assert INTER_MB_DTYPE.itemsize == 80 and C.sizeof(InterMb) == 80 and InterMb.mv.offset == 16
 
+
+
+class InterBmb(C.Structure):
+    """dryv_inter_bmb (144 bytes): one macroblock of the two-list inter prediction stage (B, weighted P)."""
+    _fields_ = [("mb_type", C.c_uint8), ("qp", C.c_uint8), ("flags", C.c_uint8), ("reserved0", C.c_uint8),
+                ("ref_idx", (C.c_int8 * 4) * 2), ("reserved", C.c_uint8 * 4), ("mv", ((C.c_int16 * 2) * 16) * 2)]
+
+
+class InterWeightEntry(C.Structure):
+    _fields_ = [("w", C.c_int16 * 3), ("o", C.c_int16 * 3), ("reserved", C.c_int16 * 2)]
+
+
+class InterWeights(C.Structure):
+    """dryv_inter_weights (1040 bytes): one picture's weighted prediction mode and tables."""
+    _fields_ = [("mode", C.c_uint8), ("luma_log2_denom", C.c_uint8), ("chroma_log2_denom", C.c_uint8), ("reserved", C.c_uint8 * 13),
+                ("expl", (InterWeightEntry * 16) * 2), ("implicit_w1", (C.c_int16 * 16) * 16)]
+
+
+WEIGHTS_DEFAULT, WEIGHTS_EXPLICIT, WEIGHTS_IMPLICIT = 0, 1, 2   # dryv_inter_weights.mode
+INTER_BMB_DTYPE = np.dtype([("mb_type", "u1"), ("qp", "u1"), ("flags", "u1"), ("reserved0", "u1"), ("ref_idx", "i1", (2, 4)),
+                            ("reserved", "u1", (4,)), ("mv", "<i2", (2, 16, 2))])
+INTER_WEIGHTS_DTYPE = np.dtype([("mode", "u1"), ("luma_log2_denom", "u1"), ("chroma_log2_denom", "u1"), ("reserved", "u1", (13,)),
+                                ("expl", [("w", "<i2", (3,)), ("o", "<i2", (3,)), ("reserved", "<i2", (2,))], (2, 16)),
+                                ("implicit_w1", "<i2", (16, 16))])
+assert INTER_BMB_DTYPE.itemsize == 144 == C.sizeof(InterBmb) and INTER_WEIGHTS_DTYPE.itemsize == 1040 == C.sizeof(InterWeights)
+
 # every function include/dryv_recon.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dryv_recon_frame_bytes": (C.c_size_t, [C.POINTER(FrameParams)]),
@@ -134,6 +160,10 @@ SYMBOLS = {
     "dryv_inter_destroy": (None, [C.c_void_p]),
     "dryv_inter_submit_device": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p),
                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dryv_inter_check_bipred": (C.c_int, [C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p]),
+    "dryv_inter_submit_device_bipred": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.c_uint32,
+                                                  C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
+                                                  C.c_void_p]),
     "dryv_inter_sync": (C.c_int, [C.c_void_p]),
     "dryv_inter_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dryv_recon_strerror": (C.c_char_p, [C.c_int]),

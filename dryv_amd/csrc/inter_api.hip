@@ -8,6 +8,7 @@
 #include "inter_launch.h"
 
 using dryv::inter::Args;
+using dryv::inter::BArgs;
 using dryv::inter::IParams;
 
 struct dryv_inter_ctx {
@@ -15,35 +16,53 @@ struct dryv_inter_ctx {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   hipEvent_t ev_start = nullptr, ev_stop = nullptr;   // the most recent launch's own start and end
-  hipEvent_t ev_tab = nullptr;                        // the most recent copy of the reference table has left h_refs
+  hipEvent_t ev_tab = nullptr;                        // the most recent submit's copies have left the staging buffers
   bool timed = false, tab_pending = false;
   unsigned* d_status = nullptr;
   unsigned* h_status = nullptr;   // pinned
-  // the reference table of the most recent submit: pinned staging + device copy, grow-only (a device copy is replaced in
-  // stream order, behind the launch that read it; the staging waits for its own copy)
-  void** h_refs = nullptr;
-  void** d_refs = nullptr;
-  size_t cap_refs = 0;
+  // what the most recent submit copied in: pinned staging + device copy, grow-only (a device copy is replaced in stream order,
+  // behind the launch that read it; the staging waits for its own copy). The reference table (list 0's for a bi-predictive
+  // submit), list 1's table, the pictures' weights.
+  struct Staged {
+    void* h = nullptr;
+    void* d = nullptr;
+    size_t cap = 0;   // bytes
+  } refs, refs1, weights;
   int num_cus = 256;
 };
 
 namespace {
 
-int ensure_refs(dryv_inter_ctx* ctx, size_t n) {
-  if (ctx->cap_refs >= n) return DRYV_OK;
-  // (the old table may still be read by launches in flight)
+void release(dryv_inter_ctx::Staged& s) {
+  if (s.h) (void)hipHostFree(s.h);
+  if (s.d) (void)hipFree(s.d);
+  s = dryv_inter_ctx::Staged();
+}
+
+int ensure(dryv_inter_ctx* ctx, dryv_inter_ctx::Staged& s, size_t bytes) {
+  if (s.cap >= bytes) return DRYV_OK;
+  // (the old copy may still be read by launches in flight)
   if (hipStreamSynchronize(ctx->stream) != hipSuccess) return DRYV_E_DEVICE;
-  if (ctx->h_refs) (void)hipHostFree(ctx->h_refs);
-  if (ctx->d_refs) (void)hipFree(ctx->d_refs);
-  ctx->h_refs = ctx->d_refs = nullptr;
-  ctx->cap_refs = 0;
+  release(s);
   ctx->tab_pending = false;
-  const size_t cap = std::max<size_t>(n, 1024);
-  if (hipHostMalloc((void**)&ctx->h_refs, cap * sizeof(void*), hipHostMallocDefault) != hipSuccess ||
-      hipMalloc((void**)&ctx->d_refs, cap * sizeof(void*)) != hipSuccess)
-    return DRYV_E_NOMEM;
-  ctx->cap_refs = cap;
+  const size_t cap = std::max<size_t>(bytes, 8192);
+  if (hipHostMalloc(&s.h, cap, hipHostMallocDefault) != hipSuccess || hipMalloc(&s.d, cap) != hipSuccess) return DRYV_E_NOMEM;
+  s.cap = cap;
   return DRYV_OK;
+}
+
+// every pointer of a reference table present and 16-byte aligned
+bool refs_ok(const void* const* tab, size_t n) {
+  for (size_t k = 0; k < n; k++)
+    if (!tab[k] || ((uintptr_t)tab[k] & 15u)) return false;
+  return true;
+}
+
+// the persistent grid of a kernel with wpb waves per workgroup and room for per_cu workgroups on a CU: the waves stride over
+// the macroblocks, so a smaller grid is merely slower
+int grid_for(const dryv_inter_ctx* ctx, int n_mbs, int wpb, int per_cu) {
+  const long long want = ((long long)n_mbs + wpb - 1) / wpb;
+  return (int)std::max(1ll, std::min(want, (long long)ctx->num_cus * per_cu));
 }
 
 }  // namespace
@@ -89,8 +108,9 @@ void dryv_inter_destroy(dryv_inter_ctx* ctx) {
   if (!ctx) return;
   (void)hipSetDevice(ctx->device);
   if (ctx->stream) (void)hipStreamSynchronize(ctx->stream);
-  if (ctx->h_refs) (void)hipHostFree(ctx->h_refs);
-  if (ctx->d_refs) (void)hipFree(ctx->d_refs);
+  release(ctx->refs);
+  release(ctx->refs1);
+  release(ctx->weights);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -109,27 +129,67 @@ int dryv_inter_submit_device(dryv_inter_ctx* ctx, const dryv_frame_params* fp, u
   // 16-byte loads of records and coefficients, 16-byte stores of the rows, aligned dword loads of the references
   if (((uintptr_t)d_mbs | (uintptr_t)d_coeffs | (uintptr_t)d_yuv_out) & 15u) return DRYV_E_INVALID;
   const size_t n_tab = (size_t)n_frames * n_refs;
-  for (size_t k = 0; k < n_tab; k++)
-    if (!d_refs[k] || ((uintptr_t)d_refs[k] & 15u)) return DRYV_E_INVALID;
+  if (!refs_ok(d_refs, n_tab)) return DRYV_E_INVALID;
   (void)hipSetDevice(ctx->device);
-  if ((st = ensure_refs(ctx, n_tab)) != DRYV_OK) return st;
+  if ((st = ensure(ctx, ctx->refs, n_tab * sizeof(void*))) != DRYV_OK) return st;
   if (ctx->tab_pending && hipEventSynchronize(ctx->ev_tab) != hipSuccess) return DRYV_E_DEVICE;
-  std::copy(d_refs, d_refs + n_tab, (const void**)ctx->h_refs);
-  if (hipMemcpyAsync(ctx->d_refs, ctx->h_refs, n_tab * sizeof(void*), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+  std::copy(d_refs, d_refs + n_tab, (const void**)ctx->refs.h);
+  if (hipMemcpyAsync(ctx->refs.d, ctx->refs.h, n_tab * sizeof(void*), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
       hipEventRecord(ctx->ev_tab, ctx->stream) != hipSuccess)
     return DRYV_E_DEVICE;
   ctx->tab_pending = true;
   Args A;
-  A.refs = (const uint8_t* const*)ctx->d_refs;
+  A.refs = (const uint8_t* const*)ctx->refs.d;
   A.mbs = (const dryv_inter_mb*)d_mbs;
   A.coeffs = (const int16_t*)d_coeffs;
   A.yuv = (uint8_t*)d_yuv_out;
   A.status = ctx->d_status;
-  // a persistent grid: the waves stride over the macroblocks, so a smaller grid is merely slower
-  const int wpb = dryv::inter::inter_waves_per_block();
-  const long long want = ((long long)P.n_mbs + wpb - 1) / wpb;
-  const int grid = (int)std::max(1ll, std::min(want, (long long)ctx->num_cus * dryv::inter::inter_blocks_per_cu()));
+  const int grid = grid_for(ctx, P.n_mbs, dryv::inter::inter_waves_per_block(), dryv::inter::inter_blocks_per_cu());
   if (dryv::inter::inter_launch(P, A, grid, ctx->stream, ctx->ev_start, ctx->ev_stop) != hipSuccess) return DRYV_E_DEVICE;
+  ctx->timed = true;
+  return DRYV_OK;
+}
+
+int dryv_inter_check_bipred(const dryv_frame_params* fp, uint32_t n_frames, uint32_t n_refs0, uint32_t n_refs1,
+                            const dryv_inter_weights* weights) {
+  return dryv::inter::build_bparams(fp, n_frames, n_refs0, n_refs1, weights, nullptr);
+}
+
+int dryv_inter_submit_device_bipred(dryv_inter_ctx* ctx, const dryv_frame_params* fp, uint32_t n_frames, uint32_t n_refs0,
+                                    uint32_t n_refs1, const void* const* d_refs0, const void* const* d_refs1,
+                                    const dryv_inter_weights* weights, const void* d_mbs, const void* d_coeffs, void* d_yuv_out) {
+  if (!ctx || !d_refs0 || (n_refs1 && !d_refs1) || !d_mbs || !d_coeffs || !d_yuv_out) return DRYV_E_INVALID;
+  IParams P;
+  int st = dryv::inter::build_bparams(fp, n_frames, n_refs0, n_refs1, weights, &P);
+  if (st != DRYV_OK) return st;
+  if (((uintptr_t)d_mbs | (uintptr_t)d_coeffs | (uintptr_t)d_yuv_out) & 15u) return DRYV_E_INVALID;
+  const size_t n0 = (size_t)n_frames * n_refs0, n1 = (size_t)n_frames * n_refs1, wb = weights ? (size_t)n_frames * sizeof(dryv_inter_weights) : 0;
+  if (!refs_ok(d_refs0, n0) || !refs_ok(d_refs1, n1)) return DRYV_E_INVALID;
+  (void)hipSetDevice(ctx->device);
+  if ((st = ensure(ctx, ctx->refs, n0 * sizeof(void*))) != DRYV_OK || (st = ensure(ctx, ctx->refs1, n1 * sizeof(void*))) != DRYV_OK ||
+      (st = ensure(ctx, ctx->weights, wb)) != DRYV_OK)
+    return st;
+  if (ctx->tab_pending && hipEventSynchronize(ctx->ev_tab) != hipSuccess) return DRYV_E_DEVICE;
+  std::copy(d_refs0, d_refs0 + n0, (const void**)ctx->refs.h);
+  if (n1) std::copy(d_refs1, d_refs1 + n1, (const void**)ctx->refs1.h);
+  if (wb) memcpy(ctx->weights.h, weights, wb);
+  if (hipMemcpyAsync(ctx->refs.d, ctx->refs.h, n0 * sizeof(void*), hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      (n1 && hipMemcpyAsync(ctx->refs1.d, ctx->refs1.h, n1 * sizeof(void*), hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ||
+      (wb && hipMemcpyAsync(ctx->weights.d, ctx->weights.h, wb, hipMemcpyHostToDevice, ctx->stream) != hipSuccess) ||
+      hipEventRecord(ctx->ev_tab, ctx->stream) != hipSuccess)
+    return DRYV_E_DEVICE;
+  ctx->tab_pending = true;
+  BArgs A;
+  A.refs[0] = (const uint8_t* const*)ctx->refs.d;
+  A.refs[1] = n1 ? (const uint8_t* const*)ctx->refs1.d : nullptr;
+  A.weights = wb ? (const dryv_inter_weights*)ctx->weights.d : nullptr;
+  A.mbs = (const dryv_inter_bmb*)d_mbs;
+  A.coeffs = (const int16_t*)d_coeffs;
+  A.yuv = (uint8_t*)d_yuv_out;
+  A.status = ctx->d_status;
+  A.n_refs1 = (int)n_refs1;
+  const int grid = grid_for(ctx, P.n_mbs, dryv::inter::inter_bi_waves_per_block(), dryv::inter::inter_bi_blocks_per_cu());
+  if (dryv::inter::inter_bi_launch(P, A, grid, ctx->stream, ctx->ev_start, ctx->ev_stop) != hipSuccess) return DRYV_E_DEVICE;
   ctx->timed = true;
   return DRYV_OK;
 }

@@ -33,8 +33,7 @@ constexpr int S_CWIN = S_LWIN + 1728;       // chroma windows, per plane 9 x 12 
 constexpr int S_RESC = S_CWIN + 768 + 16;   // i16 [2][64]: chroma residual
 constexpr int S_OUT = S_RESC + 256;         // u8 [256] Y, [64] Cb, [64] Cr: the reconstructed macroblock
 constexpr int S_BYTES = S_OUT + 384;        // 4032
-constexpr int S_TMP8 = S_LWIN;              // i32 [4][64]: 8x8 rows after the first pass
-constexpr int S_RES8 = S_LWIN + 1024;       // i16 [4][64]: 8x8 residual
+// over the luma windows, once they are read: i32 [4][64], the 8x8 rows after the first pass; at + 1024 i16 [4][64]: 8x8 residual
 static_assert(S_BYTES % 16 == 0 && S_COEF % 16 == 0 && S_LWIN % 16 == 0 && S_OUT % 16 == 0, "16-byte LDS accesses");
 
 WV void build_tables(const IParams& P, int ldsBase, int tid, int nthreads) {
@@ -62,9 +61,12 @@ WV unsigned fetch_dword(const uint8_t* p, int x, int wp) {
 
 // Stages the windows of one plane kind. Luma: window w covers blocks w << LS .. of the macroblock, origin 2 left of and 2
 // above the first block's integer position, Geo::ROWS rows of Geo::ND dwords from the aligned x at or below the origin.
-// Chroma (both planes, items interleaved): origin at the integer position.
-template <int LS, bool CHROMA>
-WV void stage(int S, int lane, int mbx, int mby, int wpix, int hpix, unsigned planeOff, unsigned planeStep) {
+// Chroma (both planes, items interleaved): origin at the integer position. mvA: LDS address of the sixteen vectors; refpA: of the
+// four quadrants' reference pointers; winA: of the windows. MASKED: items of a quadrant whose bit in `used` is clear are
+// neither loaded nor stored.
+template <int LS, bool CHROMA, bool MASKED = false>
+WV void stage(int mvA, int refpA, int winA, int lane, int mbx, int mby, int wpix, int hpix, unsigned planeOff, unsigned planeStep,
+              unsigned used = 0xfu) {
   using G = Geo<LS>;
   constexpr int ROWS = CHROMA ? G::CROWS : G::ROWS, ND = CHROMA ? G::CND : G::ND;
   constexpr int NWIN = 16 >> LS, PER = NWIN * ROWS * ND, N = CHROMA ? 2 * PER : PER;
@@ -72,9 +74,10 @@ WV void stage(int S, int lane, int mbx, int mby, int wpix, int hpix, unsigned pl
     const int pl = CHROMA ? i / PER : 0, r0 = i - pl * PER;
     const int w = r0 / (ROWS * ND), r1 = r0 - w * (ROWS * ND), row = r1 / ND, dw = r1 - row * ND;
     const int b = w << LS;
-    const unsigned mv = wv::lds_u32(S + S_REC + 16 + 4 * b);
+    if (MASKED && !((used >> (b >> 2)) & 1u)) continue;
+    const unsigned mv = wv::lds_u32(mvA + 4 * b);
     const int mvx = (int)(short)(mv & 0xffffu), mvy = (int)mv >> 16;
-    const u32x2 rp = wv::lds_u64(S + S_REFP + 8 * (b >> 2));
+    const u32x2 rp = wv::lds_u64(refpA + 8 * (b >> 2));
     const uint8_t* ref = (const uint8_t*)(((unsigned long long)rp[1] << 32) | rp[0]);
     int x0, y0;
     if (CHROMA) {
@@ -87,7 +90,7 @@ WV void stage(int S, int lane, int mbx, int mby, int wpix, int hpix, unsigned pl
     const int yy = min(max(y0 + row, 0), hpix - 1);
     const uint8_t* p = ref + (size_t)planeOff + (size_t)pl * planeStep + (size_t)((unsigned)yy * (unsigned)wpix);
     const unsigned v = fetch_dword(p, (x0 & ~3) + 4 * dw, wpix);
-    wv::lds_st32(S + (CHROMA ? S_CWIN : S_LWIN) + ((pl * NWIN + w) * ROWS + row) * (ND * 4) + 4 * dw, v);
+    wv::lds_st32(winA + ((pl * NWIN + w) * ROWS + row) * (ND * 4) + 4 * dw, v);
   }
 }
 
@@ -185,28 +188,29 @@ WV unsigned chroma_pred(int A, int pitch, int sh, int xf, int yf) {
   return p0 | p1 << 8;
 }
 
+// The lane's luma and chroma prediction samples from the windows stage<LS> left at lwinA / cwinA (vectors at mvA).
 template <int LS>
-WV void predict(int S, int lane, int mbx, int mby, unsigned* lumaOut, unsigned* chromaOut) {
+WV void predict(int mvA, int lwinA, int cwinA, int lane, int mbx, int mby, unsigned* lumaOut, unsigned* chromaOut) {
   using G = Geo<LS>;
   {
     const int b = lane >> 2, r = lane & 3;
-    const unsigned mv = wv::lds_u32(S + S_REC + 16 + 4 * b);
+    const unsigned mv = wv::lds_u32(mvA + 4 * b);
     const int mvx = (int)(short)(mv & 0xffffu), mvy = (int)mv >> 16;
     const int ox = blk_x(b) & G::MASK, oy = blk_y(b) & G::MASK;
     const int x0 = mbx * 16 + blk_x(b) - ox + (mvx >> 2) - 2;
     const int o = (x0 & 3) + ox;
-    const int A = S + S_LWIN + (((b >> LS) * G::ROWS) + oy + r) * (G::ND * 4) + (o & ~3);
+    const int A = lwinA + (((b >> LS) * G::ROWS) + oy + r) * (G::ND * 4) + (o & ~3);
     *lumaOut = luma_pred(A, G::ND * 4, o & 3, mvx & 3, mvy & 3);
   }
   {
     const int pl = lane >> 5, b = (lane & 31) >> 1, r = lane & 1;
-    const unsigned mv = wv::lds_u32(S + S_REC + 16 + 4 * b);
+    const unsigned mv = wv::lds_u32(mvA + 4 * b);
     const int mvx = (int)(short)(mv & 0xffffu), mvy = (int)mv >> 16;
     const int cx = blk_x(b) >> 1, cy = blk_y(b) >> 1;
     const int ox = cx & (G::MASK >> 1), oy = cy & (G::MASK >> 1);
     const int x0 = mbx * 8 + cx - ox + (mvx >> 3);
     const int o = (x0 & 3) + ox;
-    const int A = S + S_CWIN + (((pl * (16 >> LS) + (b >> LS)) * G::CROWS) + oy + r) * (G::CND * 4) + (o & ~3);
+    const int A = cwinA + (((pl * (16 >> LS) + (b >> LS)) * G::CROWS) + oy + r) * (G::CND * 4) + (o & ~3);
     *chromaOut = chroma_pred(A, G::CND * 4, o & 3, mvx & 7, mvy & 7);
   }
 }
@@ -263,8 +267,9 @@ WV void bf8(const int* d, int* o) {
 }
 
 // 8.5.13 for the macroblock's four 8x8 blocks: lanes 0..31, eight per block, take a row each, then a column each, through
-// LDS; the residual lands in S_RES8 as i16 [4][8][8]. (Behind the prediction: the scratch lies over the luma windows.)
-WV void resid8x8(int S, int T, int lane, int qp) {
+// LDS; the residual lands at res8A as i16 [4][8][8]; tmp8A: i32 [4][64] of scratch. (Behind the prediction: both lie over the
+// luma windows.)
+WV void resid8x8(int coefA, int tmp8A, int res8A, int T, int lane, int qp) {
   const int qd = qp / 6, m = qp - 6 * qd;
   const int q = (lane >> 3) & 3, i = lane & 7;
   if (lane < 32) {
@@ -272,20 +277,20 @@ WV void resid8x8(int S, int T, int lane, int qp) {
 #pragma unroll
     for (int j = 0; j < 8; j++) {
       const int k = (int)wv::lds_u8(T + T_ZZ8I + i * 8 + j);
-      d[j] = dequant(wv::lds_i16(S + S_COEF + 2 * (q * 64 + k)), (int)wv::lds_u16(T + T_LS8 + 2 * (m * 64 + k)), qd, 6);
+      d[j] = dequant(wv::lds_i16(coefA + 2 * (q * 64 + k)), (int)wv::lds_u16(T + T_LS8 + 2 * (m * 64 + k)), qd, 6);
     }
     bf8(d, g);
 #pragma unroll
-    for (int j = 0; j < 8; j++) wv::lds_st32(S + S_TMP8 + 4 * (q * 64 + i * 8 + j), (unsigned)g[j]);
+    for (int j = 0; j < 8; j++) wv::lds_st32(tmp8A + 4 * (q * 64 + i * 8 + j), (unsigned)g[j]);
   }
   wv::wave_sync();
   if (lane < 32) {
     int d[8], g[8];
 #pragma unroll
-    for (int y = 0; y < 8; y++) d[y] = (int)wv::lds_u32(S + S_TMP8 + 4 * (q * 64 + y * 8 + i));
+    for (int y = 0; y < 8; y++) d[y] = (int)wv::lds_u32(tmp8A + 4 * (q * 64 + y * 8 + i));
     bf8(d, g);
 #pragma unroll
-    for (int y = 0; y < 8; y++) wv::lds_st16(S + S_RES8 + 2 * (q * 64 + y * 8 + i), (unsigned)((g[y] + 32) >> 6));
+    for (int y = 0; y < 8; y++) wv::lds_st16(res8A + 2 * (q * 64 + y * 8 + i), (unsigned)((g[y] + 32) >> 6));
   }
   wv::wave_sync();
 }
@@ -297,12 +302,90 @@ WV unsigned add_clip4(unsigned pred, const int* r) {
   return out;
 }
 
+// Where a macroblock's rows go: its picture, the row pitch of the luma plane, the chroma planes' offset and distance.
+struct OutGeo {
+  uint8_t* out;
+  unsigned yStride, cOff, cStep;
+  int mbx, mby;
+};
+
+// A record outside the supported domain: the macroblock zero-filled, the status bit set.
+WV void zero_fill(const OutGeo& G, int lane, unsigned* status) {
+  if (lane < 16) wv::st_g128(G.out + (16u * (unsigned)G.mby + (unsigned)lane) * G.yStride + 16u * (unsigned)G.mbx, (u32x4){0u, 0u, 0u, 0u});
+  else if (lane < 32) {
+    const unsigned pl = (unsigned)(lane - 16) >> 3, row = (unsigned)lane & 7u;
+    wv::st_g64(G.out + G.cOff + pl * G.cStep + (8u * (unsigned)G.mby + row) * (G.yStride >> 1) + 8u * (unsigned)G.mbx, (u32x2){0u, 0u});
+  }
+  if (lane == 0) wv::atomic_or(status, 1u);
+}
+
+// The residual of the macroblock whose coefficients the lanes 0..47 hold in cq, added to the lanes' prediction samples and
+// clipped. coefA: i16 [384]; scrA: 1536 bytes of scratch for the 8x8 transform (the dead luma windows); rescA: i16 [2][64].
+WV void add_residual(int coefA, int scrA, int rescA, int T, int lane, int qp, unsigned flags, u32x4 cq, unsigned* predY, unsigned* predC) {
+  if (lane < 48) wv::lds_st128(coefA + 16 * lane, cq);
+  wv::wave_sync();
+  int r[4];
+  const int b = lane >> 2, row = lane & 3;
+  if (flags & 1u) {
+    resid8x8(coefA, scrA, scrA + 1024, T, lane, qp);
+    const u32x2 v = wv::lds_u64(scrA + 1024 + 2 * ((b >> 2) * 64 + (((b >> 1) & 1) * 4 + row) * 8 + (b & 1) * 4));
+    r[0] = lo16(v[0]);
+    r[1] = hi16(v[0]);
+    r[2] = lo16(v[1]);
+    r[3] = hi16(v[1]);
+  } else {
+    const int qd = qp / 6, m = qp - 6 * qd;
+    resid4x4_row(coefA + 32 * b, T + T_LS4 + 32 * m, qd, row, false, 0, r);
+  }
+  *predY = add_clip4(*predY, r);
+  // chroma (8.5.11): plane (l >> 4) & 1, block (l >> 2) & 3, row l & 3 (lanes 32..63 repeat 0..31: the quads stay whole);
+  // the residual goes through LDS to the lanes that own the pixels
+  {
+    const int cl = lane & 31, pl = cl >> 4, blk = (cl >> 2) & 3;
+    const int qpc = (int)wv::lds_u8(T + T_QPC + pl * 52 + qp), qd = qpc / 6, m = qpc - 6 * qd;
+    const int base = coefA + 2 * (256 + 64 * pl), lsA = T + T_LS4 + 32 * ((1 + pl) * 6 + m);
+    const int c0 = wv::lds_i16(base), c1 = wv::lds_i16(base + 2), c2 = wv::lds_i16(base + 4), c3 = wv::lds_i16(base + 6);
+    const int fdc = blk == 0 ? c0 + c1 + c2 + c3 : blk == 1 ? c0 - c1 + c2 - c3 : blk == 2 ? c0 + c1 - c2 - c3 : c0 - c1 - c2 + c3;
+    const int dcv = ((fdc * (int)wv::lds_u16(lsA)) << qd) >> 5;
+    int rc[4];
+    resid4x4_row(base + 8 + 30 * blk - 2, lsA, qd, row, true, dcv, rc);
+    const int at = rescA + 2 * (pl * 64 + ((blk >> 1) * 4 + row) * 8 + (blk & 1) * 4);
+    if (lane < 32)
+      wv::lds_st64(at, (u32x2){((unsigned)rc[0] & 0xffffu) | (unsigned)rc[1] << 16, ((unsigned)rc[2] & 0xffffu) | (unsigned)rc[3] << 16});
+  }
+  wv::wave_sync();
+  {
+    const int pl = lane >> 5, bb = (lane & 31) >> 1, rr = lane & 1;
+    const int cx = blk_x(bb) >> 1, cy = (blk_y(bb) >> 1) + rr;
+    const unsigned v = wv::lds_u32(rescA + 2 * (pl * 64 + cy * 8 + cx));
+    const unsigned c = *predC;
+    *predC = (unsigned)clip255((int)(c & 255u) + lo16(v)) | (unsigned)clip255((int)((c >> 8) & 255u) + hi16(v)) << 8;
+  }
+}
+
+// The lanes' reconstructed samples through LDS (outA: u8 [256] Y, [64] Cb, [64] Cr) to whole rows of the picture.
+WV void write_out(const OutGeo& G, int outA, int lane, unsigned predY, unsigned predC) {
+  {
+    const int b = lane >> 2, row = lane & 3;
+    wv::lds_st32(outA + (blk_y(b) + row) * 16 + blk_x(b), predY);
+    const int pl = lane >> 5, bb = (lane & 31) >> 1, rr = lane & 1;
+    wv::lds_st16(outA + 256 + pl * 64 + ((blk_y(bb) >> 1) + rr) * 8 + (blk_x(bb) >> 1), predC);
+  }
+  wv::wave_sync();
+  if (lane < 16) wv::st_g128(G.out + (16u * (unsigned)G.mby + (unsigned)lane) * G.yStride + 16u * (unsigned)G.mbx, wv::lds_u128(outA + 16 * lane));
+  else if (lane < 32) {
+    const unsigned pl = (unsigned)(lane - 16) >> 3, row = (unsigned)lane & 7u;
+    wv::st_g64(G.out + G.cOff + pl * G.cStep + (8u * (unsigned)G.mby + row) * (G.yStride >> 1) + 8u * (unsigned)G.mbx,
+               wv::lds_u64(outA + 256 + 8 * (lane - 16)));
+  }
+}
+
 // One macroblock: index a of the batch.
 WV void inter_mb(const IParams& P, const Args& A, int T, int S, int lane, int a) {
   const int per = P.W * P.H;
   const int f = a / per, within = a - f * per, mby = within / P.W, mbx = within - mby * P.W;
-  uint8_t* out = A.yuv + (size_t)f * (size_t)per * 384u;
-  const unsigned yStride = 16u * (unsigned)P.W, cOff = 256u * (unsigned)per, cStep = 64u * (unsigned)per;
+  const unsigned cOff = 256u * (unsigned)per, cStep = 64u * (unsigned)per;
+  const OutGeo G = {A.yuv + (size_t)f * (size_t)per * 384u, 16u * (unsigned)P.W, cOff, cStep, mbx, mby};
 
   if (lane < 20) wv::lds_st32(S + S_REC + 4 * lane, ((const unsigned*)(A.mbs + a))[lane]);
   wv::wave_sync();
@@ -312,12 +395,7 @@ WV void inter_mb(const IParams& P, const Args& A, int T, int S, int lane, int a)
   const int myRef = (int)(signed char)wv::lds_u8(S + S_REC + 4 + (lane & 3));
   const bool bad = (head & 255u) != 0u || qp > 51 || wv::any(myRef < 0 || myRef >= P.n_refs);
   if (bad) {   // outside the supported domain: zero-filled, reported; the reference table is not read
-    if (lane < 16) wv::st_g128(out + (16u * (unsigned)mby + (unsigned)lane) * yStride + 16u * (unsigned)mbx, (u32x4){0u, 0u, 0u, 0u});
-    else if (lane < 32) {
-      const unsigned pl = (unsigned)(lane - 16) >> 3, row = (unsigned)lane & 7u;
-      wv::st_g64(out + cOff + pl * cStep + (8u * (unsigned)mby + row) * (yStride >> 1) + 8u * (unsigned)mbx, (u32x2){0u, 0u});
-    }
-    if (lane == 0) wv::atomic_or(A.status, 1u);
+    zero_fill(G, lane, A.status);
     return;
   }
   if (lane < 4) {
@@ -328,84 +406,34 @@ WV void inter_mb(const IParams& P, const Args& A, int T, int S, int lane, int a)
   u32x4 cq = {0u, 0u, 0u, 0u};
   if (hasRes && lane < 48) cq = ((const u32x4*)(A.coeffs + (size_t)a * 384u))[lane];
   // the level of the windows: wave-uniform
-  const unsigned myMv = wv::lds_u32(S + S_REC + 16 + 4 * (lane & 15));
-  const bool same16 = !wv::any(myMv != wv::lds_u32(S + S_REC + 16) || myRef != (int)(signed char)wv::lds_u8(S + S_REC + 4));
-  const bool same4 = !wv::any(myMv != wv::lds_u32(S + S_REC + 16 + 4 * (lane & 12)));
+  const int mvA = S + S_REC + 16, refpA = S + S_REFP, lwinA = S + S_LWIN, cwinA = S + S_CWIN;
+  const unsigned myMv = wv::lds_u32(mvA + 4 * (lane & 15));
+  const bool same16 = !wv::any(myMv != wv::lds_u32(mvA) || myRef != (int)(signed char)wv::lds_u8(S + S_REC + 4));
+  const bool same4 = !wv::any(myMv != wv::lds_u32(mvA + 4 * (lane & 12)));
   wv::wave_sync();   // the reference pointers
   unsigned predY, predC;
   const int wl = 16 * P.W, hl = 16 * P.H;
   if (same16) {
-    stage<4, false>(S, lane, mbx, mby, wl, hl, 0u, 0u);
-    stage<4, true>(S, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
+    stage<4, false>(mvA, refpA, lwinA, lane, mbx, mby, wl, hl, 0u, 0u);
+    stage<4, true>(mvA, refpA, cwinA, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
     wv::wave_sync();
-    predict<4>(S, lane, mbx, mby, &predY, &predC);
+    predict<4>(mvA, lwinA, cwinA, lane, mbx, mby, &predY, &predC);
   } else if (same4) {
-    stage<2, false>(S, lane, mbx, mby, wl, hl, 0u, 0u);
-    stage<2, true>(S, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
+    stage<2, false>(mvA, refpA, lwinA, lane, mbx, mby, wl, hl, 0u, 0u);
+    stage<2, true>(mvA, refpA, cwinA, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
     wv::wave_sync();
-    predict<2>(S, lane, mbx, mby, &predY, &predC);
+    predict<2>(mvA, lwinA, cwinA, lane, mbx, mby, &predY, &predC);
   } else {
-    stage<0, false>(S, lane, mbx, mby, wl, hl, 0u, 0u);
-    stage<0, true>(S, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
+    stage<0, false>(mvA, refpA, lwinA, lane, mbx, mby, wl, hl, 0u, 0u);
+    stage<0, true>(mvA, refpA, cwinA, lane, mbx, mby, wl >> 1, hl >> 1, cOff, cStep);
     wv::wave_sync();
-    predict<0>(S, lane, mbx, mby, &predY, &predC);
+    predict<0>(mvA, lwinA, cwinA, lane, mbx, mby, &predY, &predC);
   }
   wv::wave_sync();   // the windows are read: their LDS is the 8x8 transform's scratch from here on
 
-  if (wv::any((cq[0] | cq[1] | cq[2] | cq[3]) != 0u)) {   // (never under flag bit1: cq is 0 then)
-    if (lane < 48) wv::lds_st128(S + S_COEF + 16 * lane, cq);
-    wv::wave_sync();
-    int r[4];
-    const int b = lane >> 2, row = lane & 3;
-    if (flags & 1u) {
-      resid8x8(S, T, lane, qp);
-      const u32x2 v = wv::lds_u64(S + S_RES8 + 2 * ((b >> 2) * 64 + (((b >> 1) & 1) * 4 + row) * 8 + (b & 1) * 4));
-      r[0] = lo16(v[0]);
-      r[1] = hi16(v[0]);
-      r[2] = lo16(v[1]);
-      r[3] = hi16(v[1]);
-    } else {
-      const int qd = qp / 6, m = qp - 6 * qd;
-      resid4x4_row(S + S_COEF + 32 * b, T + T_LS4 + 32 * m, qd, row, false, 0, r);
-    }
-    predY = add_clip4(predY, r);
-    // chroma (8.5.11): plane (l >> 4) & 1, block (l >> 2) & 3, row l & 3 (lanes 32..63 repeat 0..31: the quads stay whole);
-    // the residual goes through LDS to the lanes that own the pixels
-    {
-      const int cl = lane & 31, pl = cl >> 4, blk = (cl >> 2) & 3;
-      const int qpc = (int)wv::lds_u8(T + T_QPC + pl * 52 + qp), qd = qpc / 6, m = qpc - 6 * qd;
-      const int base = S + S_COEF + 2 * (256 + 64 * pl), lsA = T + T_LS4 + 32 * ((1 + pl) * 6 + m);
-      const int c0 = wv::lds_i16(base), c1 = wv::lds_i16(base + 2), c2 = wv::lds_i16(base + 4), c3 = wv::lds_i16(base + 6);
-      const int fdc = blk == 0 ? c0 + c1 + c2 + c3 : blk == 1 ? c0 - c1 + c2 - c3 : blk == 2 ? c0 + c1 - c2 - c3 : c0 - c1 - c2 + c3;
-      const int dcv = ((fdc * (int)wv::lds_u16(lsA)) << qd) >> 5;
-      int rc[4];
-      resid4x4_row(base + 8 + 30 * blk - 2, lsA, qd, row, true, dcv, rc);
-      const int at = S + S_RESC + 2 * (pl * 64 + ((blk >> 1) * 4 + row) * 8 + (blk & 1) * 4);
-      if (lane < 32)
-        wv::lds_st64(at, (u32x2){((unsigned)rc[0] & 0xffffu) | (unsigned)rc[1] << 16, ((unsigned)rc[2] & 0xffffu) | (unsigned)rc[3] << 16});
-    }
-    wv::wave_sync();
-    {
-      const int pl = lane >> 5, bb = (lane & 31) >> 1, rr = lane & 1;
-      const int cx = blk_x(bb) >> 1, cy = (blk_y(bb) >> 1) + rr;
-      const unsigned v = wv::lds_u32(S + S_RESC + 2 * (pl * 64 + cy * 8 + cx));
-      predC = (unsigned)clip255((int)(predC & 255u) + lo16(v)) | (unsigned)clip255((int)((predC >> 8) & 255u) + hi16(v)) << 8;
-    }
-  }
-  // out: through LDS to whole rows
-  {
-    const int b = lane >> 2, row = lane & 3;
-    wv::lds_st32(S + S_OUT + (blk_y(b) + row) * 16 + blk_x(b), predY);
-    const int pl = lane >> 5, bb = (lane & 31) >> 1, rr = lane & 1;
-    wv::lds_st16(S + S_OUT + 256 + pl * 64 + ((blk_y(bb) >> 1) + rr) * 8 + (blk_x(bb) >> 1), predC);
-  }
-  wv::wave_sync();
-  if (lane < 16) wv::st_g128(out + (16u * (unsigned)mby + (unsigned)lane) * yStride + 16u * (unsigned)mbx, wv::lds_u128(S + S_OUT + 16 * lane));
-  else if (lane < 32) {
-    const unsigned pl = (unsigned)(lane - 16) >> 3, row = (unsigned)lane & 7u;
-    wv::st_g64(out + cOff + pl * cStep + (8u * (unsigned)mby + row) * (yStride >> 1) + 8u * (unsigned)mbx,
-               wv::lds_u64(S + S_OUT + 256 + 8 * (lane - 16)));
-  }
+  if (wv::any((cq[0] | cq[1] | cq[2] | cq[3]) != 0u))   // (never under flag bit1: cq is 0 then)
+    add_residual(S + S_COEF, S + S_LWIN, S + S_RESC, T, lane, qp, flags, cq, &predY, &predC);
+  write_out(G, S + S_OUT, lane, predY, predC);
 }
 
 // The wave's loop: macroblocks first, first + stride, ...

@@ -32,6 +32,17 @@ struct Args {
   unsigned* status;             // bit 0: a record outside the supported domain
 };
 
+// The bi-predictive / weighted kernel's (inter_bi_kernel.h); n_refs0 is IParams::n_refs.
+struct BArgs {
+  const uint8_t* const* refs[2];       // device copies of the caller's tables: [n_frames][n_refsX]
+  const dryv_inter_weights* weights;   // device copy, [n_frames]; NULL: default prediction everywhere
+  const dryv_inter_bmb* mbs;
+  const int16_t* coeffs;
+  uint8_t* yuv;
+  unsigned* status;                    // bit 0: a record outside the supported domain
+  int n_refs1;                         // 0..16
+};
+
 // dryv_recon_check_params + the bound on n_refs; fills P when given.
 inline int build_iparams(const dryv_frame_params* fp, uint32_t n_frames, uint32_t n_refs, IParams* P) {
   KParams K;
@@ -76,6 +87,20 @@ inline int build_iparams(const dryv_frame_params* fp, uint32_t n_frames, uint32_
       const int qpi = std::min(std::max(qp + (pl ? K.cqo_cr : K.cqo_cb), 0), 51);
       t[T_QPC + pl * 52 + qp] = (uint8_t)(qpi < 30 ? qpi : QPC[qpi - 30]);
     }
+  return DRYV_OK;
+}
+
+// The same for the bi-predictive entry points: n_refs0 1..16, n_refs1 0..16, and the weights (host, [n_frames], or NULL) within
+// what the kernel shifts by and indexes with.
+inline int build_bparams(const dryv_frame_params* fp, uint32_t n_frames, uint32_t n_refs0, uint32_t n_refs1,
+                         const dryv_inter_weights* weights, IParams* P) {
+  const int st = build_iparams(fp, n_frames, n_refs0, P);
+  if (st != DRYV_OK) return st;
+  if (n_refs1 > 16) return DRYV_E_INVALID;
+  for (uint32_t f = 0; weights && f < n_frames; f++) {
+    if (weights[f].mode > 2) return DRYV_E_INVALID;
+    if (weights[f].mode == 1 && (weights[f].luma_log2_denom > 7 || weights[f].chroma_log2_denom > 7)) return DRYV_E_INVALID;
+  }
   return DRYV_OK;
 }
 

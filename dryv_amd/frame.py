@@ -204,7 +204,7 @@ class ReconContext:
 
 
 class InterContext:
-    """One dryv_inter_ctx: the inter prediction stage (P macroblocks, H.264 8.4.2.2 + residual) on `device`, on a stream of
+    """One dryv_inter_ctx: the inter prediction stage (P, B and weighted macroblocks, H.264 8.4.2.2 - 8.4.2.3 + residual) on `device`, on a stream of
     its own or on a borrowed one (`stream`: a raw hipStream_t, e.g. ReconContext.stream: the stage then runs behind
     reconstruction on that stream). Not thread-safe."""
 
@@ -241,6 +241,26 @@ class InterContext:
         tab = (C.c_void_p * max(len(flat), 1))(*flat)
         _check(self._lib.dryv_inter_submit_device(self._h, C.byref(fp), int(n_frames), n_refs, tab, C.c_void_p(d_mbs),
                                                   C.c_void_p(d_coeffs), C.c_void_p(d_yuv_out)))
+
+    def submit_device_bipred(self, fp, n_frames, refs0, refs1, weights, d_mbs, d_coeffs, d_yuv_out):
+        """The two-list entry point (B pictures, weighted prediction). refs0 / refs1: n_frames sequences of n_refs0 / n_refs1 raw
+        device pointers (refs1 may be empty sequences: weighted-P pictures); weights: an abi.INTER_WEIGHTS_DTYPE array of n_frames
+        entries, or None (default prediction); d_mbs: abi.INTER_BMB_DTYPE records; the rest as submit_device."""
+        tabs = []
+        for refs in (refs0, refs1):
+            flat = [int(p) for per_frame in refs for p in per_frame]
+            n = len(flat) // int(n_frames) if n_frames else 0
+            if n * int(n_frames) != len(flat) or any(len(r) != n for r in refs):
+                raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
+            tabs.append((n, (C.c_void_p * max(len(flat), 1))(*flat)))
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=abi.INTER_WEIGHTS_DTYPE).reshape(-1)
+            if w.size != int(n_frames):
+                raise ReconError(abi.DRYV_E_INVALID, "weights must have one entry per frame")
+        _check(self._lib.dryv_inter_submit_device_bipred(self._h, C.byref(fp), int(n_frames), tabs[0][0], tabs[1][0], tabs[0][1],
+                                                         tabs[1][1], None if w is None else w.ctypes.data, C.c_void_p(d_mbs),
+                                                         C.c_void_p(d_coeffs), C.c_void_p(d_yuv_out)))
 
     def sync(self, allow_unsupported=False):
         st = self._lib.dryv_inter_sync(self._h)

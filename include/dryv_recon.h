@@ -222,8 +222,8 @@ void *dryv_recon_stream(dryv_recon_ctx *ctx);
  * standard itself. A stage object of its own, next to dryv_recon_ctx.
  *
  * Not done here, by the caller instead: motion-vector prediction and P_Skip inference (records carry final vectors; a skipped
- * macroblock is one vector on all 16 blocks plus flag bit1). Not supported: B slices, bi-prediction, explicit weighted
- * prediction, field / MBAFF, intra macroblocks inside P pictures (mb_type != 0: status bit, DRYV_E_UNSUPPORTED at sync, the
+ * macroblock is one vector on all 16 blocks plus flag bit1). B macroblocks and weighted prediction: dryv_inter_submit_device_bipred
+ * below. Not supported: field / MBAFF, intra macroblocks inside P pictures (mb_type != 0: status bit, DRYV_E_UNSUPPORTED at sync, the
  * macroblock zero-filled), deblocking of inter edges.
  *
  * Reference pictures: each a full coded picture in this library's own output layout (dryv_recon_frame_bytes), 16-byte aligned.
@@ -265,6 +265,58 @@ int dryv_inter_submit_device(dryv_inter_ctx *ctx, const dryv_frame_params *fp, u
 int dryv_inter_sync(dryv_inter_ctx *ctx);
 /* Device time of the most recent launch (the dispatch's own start and end). Valid after dryv_inter_sync. */
 int dryv_inter_last_kernel_ms(dryv_inter_ctx *ctx, float *ms);
+
+/* ---- inter prediction stage, two lists: B macroblocks and weighted prediction ------------------------------------------------
+ * ITU-T H.264 8.4.2.3 (weighted sample prediction: default, explicit, implicit) over up to two motion-compensated predictions
+ * (8.4.2.2) per 8x8 quadrant: B pictures, and P pictures with explicit weights (n_refs1 = 0). Interpolation, edge clamping, the
+ * residual path with the inter scaling lists, the flags and the coefficient slots are those of the P entry point above; B
+ * pictures use the same inter lists. The entry point shares the stage's stream, status word, dryv_inter_sync and
+ * dryv_inter_last_kernel_ms with dryv_inter_submit_device; calls of either kind may be mixed before one sync and run in order.
+ *
+ * Per quadrant and plane the prediction is Clip1(((p0 * w0 + p1 * w1 + rnd) >> sh) + off) in int32 with an arithmetic shift:
+ *   one list, default, or implicit with one list:  w 1, 0          rnd 0                             sh 0          off 0
+ *   two lists, default:                            w 1, 1          rnd 1                             sh 1          off 0
+ *   explicit, one list X:                          w wX, 0         rnd denom ? 1 << (denom - 1) : 0  sh denom      off oX
+ *   explicit, two lists:                           w w0, w1        rnd 1 << denom                    sh denom + 1  off (o0 + o1 + 1) >> 1
+ *   implicit, two lists:                           w 64 - w1, w1   rnd 32                            sh 6          off 0
+ *
+ * Still the caller's: direct and skip vector derivation (spatial or temporal), reference list construction, the implicit
+ * weights from POC distances, intra macroblocks in B pictures (reported and zero-filled), field / MBAFF, deblocking of inter
+ * edges. */
+typedef struct dryv_inter_bmb {  /* 144 bytes, raster order, frames concatenated */
+  uint8_t mb_type;               /* 0 = inter. Anything else: unsupported, zero-filled */
+  uint8_t qp;                    /* QPY 0..51 (above: unsupported) */
+  uint8_t flags;                 /* bit0 transform_size_8x8_flag; bit1 no residual (slot not read): as dryv_inter_mb */
+  uint8_t reserved0;
+  int8_t ref_idx[2][4];          /* [list][8x8 quadrant]; < 0: the list is not used by that quadrant (predFlagLX = 0); a used index
+                                    >= n_refsX, or a quadrant that uses neither list: unsupported, the tables are not read */
+  uint8_t reserved[4];
+  int16_t mv[2][16][2];          /* [list][4x4 block, figure 6-10 order][x, y], quarter luma samples; ignored where the list is unused */
+} dryv_inter_bmb;
+
+typedef struct dryv_inter_weights {          /* 1040 bytes, one per picture of the batch */
+  uint8_t mode;                  /* 0 default (8.4.2.3.1), 1 explicit, 2 implicit */
+  uint8_t luma_log2_denom;       /* 0..7, explicit only */
+  uint8_t chroma_log2_denom;     /* 0..7, explicit only */
+  uint8_t reserved[13];
+  struct { int16_t w[3]; int16_t o[3]; int16_t reserved[2]; } expl[2][16];   /* [list][refIdx], planes Y, Cb, Cr: w -128..128, o -128..127;
+                                    the caller writes w = 1 << denom, o = 0 where the slice's luma/chroma_weight_lX_flag is 0 */
+  int16_t implicit_w1[16][16];   /* [refIdxL0][refIdxL1]: w1 of 8.4.2.3.2 (-64..128), w0 = 64 - w1, logWD 5, o 0; derived from POCs by the caller */
+} dryv_inter_weights;
+
+/* dryv_recon_check_params plus 1 <= n_refs0 <= 16, n_refs1 <= 16, and for every picture of weights (a HOST array [n_frames], or
+ * NULL: default everywhere) mode <= 2 and, under mode 1, both denominators <= 7 (DRYV_E_INVALID otherwise); no device needed. */
+int dryv_inter_check_bipred(const dryv_frame_params *fp, uint32_t n_frames, uint32_t n_refs0, uint32_t n_refs1,
+                            const dryv_inter_weights *weights);
+/* Predicts and reconstructs n_frames pictures of dryv_inter_bmb records into d_yuv_out. d_refs0 / d_refs1 are HOST arrays
+ * [n_frames][n_refsX] of device pointers (d_refs1 may be NULL when n_refs1 is 0: weighted-P pictures); weights is a HOST array
+ * [n_frames] or NULL; all three are copied before the call returns. Checks as dryv_inter_check_bipred; alignment, ordering and
+ * sync as dryv_inter_submit_device. */
+int dryv_inter_submit_device_bipred(dryv_inter_ctx *ctx, const dryv_frame_params *fp, uint32_t n_frames,
+                                    uint32_t n_refs0, uint32_t n_refs1,
+                                    const void *const *d_refs0, const void *const *d_refs1,
+                                    const dryv_inter_weights *weights,
+                                    const void *d_mbs, const void *d_coeffs, void *d_yuv_out);
 
 const char *dryv_recon_strerror(int status);
 const char *dryv_recon_last_device_error(dryv_recon_ctx *ctx);

@@ -4,7 +4,13 @@ picture of the same index (the bench batch, resident in HBM). Random vectors wit
 one vector (half of those without residual: P_Skip), 15 % one per quadrant, 15 % one per 4x4 block. Kernel time from the
 stage's HIP events, macroblocks/s, and the roofline arithmetic of bench.py with 1616 algorithmic bytes per macroblock (80 of
 the record + 768 of coefficients + 384 of the reference read once + 384 written). Checks the first picture against the
-restatement of the standard in tests/test_inter.py. usage: inter_rate.py [frames] [--out file.json]"""
+restatement of the standard in tests/test_inter.py. usage: inter_rate.py [frames] [--out file.json]
+
+--bipred: after the P run, in the same process, the same number of B pictures through dryv_inter_submit_device_bipred: list 0 is
+picture f's I picture, list 1 picture f + 1's; both lists' vectors have the P run's statistics; every quadrant draws L0 / L1 /
+both with a third each; default weights. Records both kernel times and their ratio (expected: below 2, since residual and
+output are shared) and checks the top of the first B picture against tests/test_inter_bipred.py. Default --out:
+profiles/inter_rate_bipred.json."""
 import json
 import os
 import sys
@@ -40,11 +46,35 @@ def p_pictures(per, rng):
     return mbs, co.reshape(n, 384)
 
 
+def b_pictures(per, mbs, rng):
+    """The P records widened: list 1's vectors drawn like list 0's, every quadrant on L0 / L1 / both."""
+    other, _ = p_pictures(per, rng)
+    b = np.zeros(len(mbs), dtype=abi.INTER_BMB_DTYPE)
+    b["qp"], b["flags"] = mbs["qp"], mbs["flags"]
+    b["mv"][:, 0], b["mv"][:, 1] = mbs["mv"], other["mv"]
+    use = rng.integers(0, 3, size=(len(mbs), 4))   # 0 L0, 1 L1, 2 both
+    b["ref_idx"][:, 0][use == 1] = -1
+    b["ref_idx"][:, 1][use == 0] = -1
+    return b
+
+
+def timed(ictx, submit):
+    times = []
+    for rep in range(12):
+        submit()
+        ictx.sync()
+        if rep >= 2:
+            times.append(ictx.last_kernel_ms())
+    return times
+
+
 def main():
     import torch
     from test_inter import reference
     frames = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 300
-    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else None
+    bipred = "--bipred" in sys.argv
+    out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else (
+        os.path.join(ROOT, "profiles", "inter_rate_bipred.json") if bipred else None)
     fp, imbs, ico, n = synth.workload("C2_1080p_intra_4x4", n_frames=frames)
     per = fp.pic_width_in_mbs * fp.pic_height_in_mbs
     mbs, co = p_pictures(per, np.random.default_rng(12))
@@ -58,12 +88,13 @@ def main():
         rctx.submit_device(fp, n, d_im.data_ptr(), d_ic.data_ptr(), d_i.data_ptr())
         rctx.sync()
         refs = [[d_i.data_ptr() + f * per * 384] for f in range(n)]
-        times = []
-        for rep in range(12):
-            ictx.submit_device(fp, n, refs, d_m.data_ptr(), d_c.data_ptr(), d_p.data_ptr())
-            ictx.sync()
-            if rep >= 2:
-                times.append(ictx.last_kernel_ms())
+        times = timed(ictx, lambda: ictx.submit_device(fp, n, refs, d_m.data_ptr(), d_c.data_ptr(), d_p.data_ptr()))
+        if bipred:
+            bmbs = b_pictures(per, mbs, np.random.default_rng(13))
+            d_bm = torch.from_numpy(bmbs.view(np.uint8).reshape(-1, 144)).cuda().repeat(reps, 1)[:n * per].contiguous()
+            d_b = torch.zeros(n * per * 384, dtype=torch.uint8, device="cuda")
+            refs1 = [[d_i.data_ptr() + ((f + 1) % n) * per * 384] for f in range(n)]
+            btimes = timed(ictx, lambda: ictx.submit_device_bipred(fp, n, refs, refs1, None, d_bm.data_ptr(), d_c.data_ptr(), d_b.data_ptr()))
     ms = float(np.mean(times))
     st, want = reference(fp, 1, [[d_i[:per * 384].cpu().numpy()]], mbs[:per], co[:per])
     ok = bool(st == 0 and np.array_equal(d_p[:per * 384].cpu().numpy(), want))
@@ -74,6 +105,26 @@ def main():
     print("inter: %.3f ms per %d frames = %.2f G macroblocks/s = %.0f GB/s algorithmic (%.3f of 8 TB/s); first picture == reference: %s"
           % (ms, n, mbps / 1e9, mbps * BYTES_PER_MB / 1e9, mbps * BYTES_PER_MB / 8e12, ok))
     assert ok
+    if bipred:
+        from test_inter_bipred import reference as b_reference
+        # (the reference is three passes of Python ints: the top eight macroblock rows as a picture of their own, compared on the
+        # top six, which no vector of +-16 samples takes below the eighth)
+        W, H = fp.pic_width_in_mbs, fp.pic_height_in_mbs
+        R, keep = min(8, H), min(8, H) - (2 if H > 8 else 0)
+        top = lambda pic, tot, rows: np.concatenate([pic[:256 * W * rows], pic[256 * W * tot:256 * W * tot + 64 * W * rows],
+                                                     pic[320 * W * tot:320 * W * tot + 64 * W * rows]])
+        fpc = abi.FrameParams.from_buffer_copy(fp)
+        fpc.pic_height_in_mbs = R
+        pics = [[top(d_i[f * per * 384:(f + 1) * per * 384].cpu().numpy(), H, R)] for f in (0, 1 % n)]
+        st, want = b_reference(fpc, 1, pics[:1], pics[1:], None, bmbs[:W * R], co[:W * R])
+        bok = bool(st == 0 and np.array_equal(top(d_b[:per * 384].cpu().numpy(), H, keep), top(want, R, keep)))
+        bms = float(np.mean(btimes))
+        res = {"frames": n, "p": res, "bipred": {"kernel_ms_avg": bms, "kernel_ms_min": float(np.min(btimes)),
+                                                 "macroblocks_per_s": n * per / (bms * 1e-3), "first_picture_matches_reference": bok},
+               "bipred_over_p": bms / ms, "expected": "below 2: residual and output are shared", "expectation_held": bool(bms / ms < 2)}
+        print("bipred: %.3f ms per %d frames = %.2f x the P batch of this session (expected below 2); first picture == reference: %s"
+              % (bms, n, bms / ms, bok))
+        assert bok
     if out_path:
         json.dump(res, open(out_path, "w"), indent=1)
 
