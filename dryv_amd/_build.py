@@ -50,8 +50,9 @@ def build_recon(force=False):
                    os.path.join(HERE, "..", "include", "dryv_recon.h")]
     # the inter prediction stage: objects of their own, compiled without packed-fp32 instruction selection, linked into
     # the same library (the other sources' command line is what bench.py's numbers were measured with: unchanged)
-    inter_srcs = [os.path.join(CSRC, f) for f in ("inter.hip", "inter_bi.hip", "inter_api.hip")]
-    deps += inter_srcs + [os.path.join(CSRC, f) for f in ("inter_kernel.h", "inter_bi_kernel.h", "inter_launch.h", "inter_params.h")]
+    inter_srcs = [os.path.join(CSRC, f) for f in ("inter.hip", "inter_bi.hip", "deblock_bs.hip", "inter_deblock.hip", "inter_api.hip")]
+    deps += inter_srcs + [os.path.join(CSRC, f) for f in ("inter_kernel.h", "inter_bi_kernel.h", "inter_launch.h", "inter_params.h",
+                                                          "deblock_bs_kernel.h")]
     os.makedirs(LIB, exist_ok=True)
     if force or _stale(RECON_SO, deps):
         objs = []

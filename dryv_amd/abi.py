@@ -125,6 +125,15 @@ INTER_WEIGHTS_DTYPE = np.dtype([("mode", "u1"), ("luma_log2_denom", "u1"), ("chr
                                 ("implicit_w1", "<i2", (16, 16))])
 assert INTER_BMB_DTYPE.itemsize == 144 == C.sizeof(InterBmb) and INTER_WEIGHTS_DTYPE.itemsize == 1040 == C.sizeof(InterWeights)
 
+
+class BsRec(C.Structure):
+    """dryv_bs_rec (16 bytes): one macroblock's boundary strengths, v[dir][edge] = four 4-bit values (segment k in bits 4k..4k+3)."""
+    _fields_ = [("v", ((C.c_uint8 * 2) * 4) * 2)]
+
+
+BS_REC_DTYPE = np.dtype([("v", "<u2", (2, 4))])   # the 16-bit words: bS of (dir, edge, segment k) = (v[dir, edge] >> 4 * k) & 15
+assert BS_REC_DTYPE.itemsize == 16 == C.sizeof(BsRec)
+
 # every function include/dryv_recon.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "dryv_recon_frame_bytes": (C.c_size_t, [C.POINTER(FrameParams)]),
@@ -164,6 +173,11 @@ SYMBOLS = {
     "dryv_inter_submit_device_bipred": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.c_uint32, C.c_uint32, C.c_uint32,
                                                   C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p, C.c_void_p, C.c_void_p,
                                                   C.c_void_p]),
+    "dryv_inter_check_deblock": (C.c_int, [C.POINTER(FrameParams), C.POINTER(DeblockParams), C.c_uint32, C.c_int, C.c_uint32, C.c_uint32]),
+    "dryv_inter_deblock_device": (C.c_int, [C.c_void_p, C.POINTER(FrameParams), C.POINTER(DeblockParams), C.c_uint32, C.c_int,
+                                            C.c_uint32, C.c_uint32, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_void_p]),
+    "dryv_inter_last_deblock_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float), C.POINTER(C.c_float)]),
     "dryv_inter_sync": (C.c_int, [C.c_void_p]),
     "dryv_inter_last_kernel_ms": (C.c_int, [C.c_void_p, C.POINTER(C.c_float)]),
     "dryv_recon_strerror": (C.c_char_p, [C.c_int]),

@@ -1,8 +1,11 @@
 // deblock_kernel.h — the in-loop deblocking filter (ITU-T H.264 8.7) for gfx950, as wave-level code (wave.h).
 //
-// Scope: frame macroblocks, 4:2:0, 8 bit, one slice per picture, all macroblocks intra: bS is 4 on
-// macroblock edges and 3 inside. dryv has no deblocking (README.md:15), so there is no reference behaviour: the checker is
-// oracle/dryv_deblock.c, a restatement of the clause.
+// Scope: frame macroblocks, 4:2:0, 8 bit, one slice per picture. Two variants of one wave function:
+//   * deblock_wave<LUMA>: all macroblocks intra (dryv_mb_desc records): bS is 4 on macroblock edges and 3 inside;
+//   * deblock_wave<LUMA, true>: P and B pictures of the inter stage: bS 0..4 per edge segment from the dryv_bs_rec records
+//     that deblock_bs_kernel.h derives, qp from the inter records. Same bands, steps, tile, rings, side buffer and hand-off.
+// dryv has no deblocking (README.md:15), so there is no reference behaviour: the checker is oracle/dryv_deblock.c, a
+// restatement of the clause (the bS-record variant: tests/test_inter_deblock.py's).
 //
 // Decomposition: the reconstruction kernel's (band_kernel.h). The filter has the same 2:1 dependency wavefront as intra
 // prediction -- macroblock (x, r) filters its left and top macroblock edges, so it needs (x-1, r), (x, r-1) and, because
@@ -39,10 +42,16 @@ struct Args {
   unsigned* taskCounter[2];
   unsigned* prog[2];       // [frame][band]: macroblocks of the band's last row whose bottom rows are in the side buffer
   uint8_t* side[2];        // [frame][band][W][64]: 4 luma rows x 16   /   [frame][band][W][32]: Cb rows 6, 7 and Cr rows 6, 7 x 8
+  // the bS-record variant only (mbs is then unused):
+  const uint8_t* recs;     // dryv_inter_mb / dryv_inter_bmb records: byte 1 is qp
+  const u32x4* bs;         // dryv_bs_rec per macroblock
+  unsigned recStride;      // 80 / 144
 };
 
 // per-workgroup tables
 constexpr int T_ALPHA = 0, T_BETA = 64, T_TC0 = 128, T_QPC = 192, T_END = 320;
+// the bS-record variant's tC0 columns behind them: u8 [3 (bS 1, 2, 3)][64]
+constexpr int T_TCB = T_END, T_END_BS = T_TCB + 192;
 // per-wave scratch
 constexpr int LSTR = 36;                      // luma tile row: 2 macroblocks x 16 + 4 (bank spread)
 constexpr int S_TILE = 0;                     // u8 [4][20][LSTR]  row j = y + 4
@@ -68,6 +77,14 @@ WV void build_tables(const DParams& P, int ldsBase, int tid, int nthreads) {
   }
 }
 
+WV void build_tables_bs(const DParams& P, int ldsBase, int tid, int nthreads) {
+  for (int k = tid; k < 52; k += nthreads) {
+    wv::lds_st8(ldsBase + T_TCB + k, P.tc0_bs1[k]);
+    wv::lds_st8(ldsBase + T_TCB + 64 + k, P.tc0_bs2[k]);
+    wv::lds_st8(ldsBase + T_TCB + 128 + k, P.tc0[k]);
+  }
+}
+
 struct Thr {
   int alpha, beta, tc0;
 };
@@ -81,9 +98,25 @@ WV Thr thresholds(int ldsBase, int qp_p, int qp_q, int offA, int offB) {
   t.tc0 = (int)wv::lds_u8(ldsBase + T_TC0 + ia);
   return t;
 }
+// the same with tC0 from table 8-17's column of this lane's bS (1..3; 0 and 4 do not use it)
+WV Thr thresholds_bs(int ldsBase, int qp_p, int qp_q, int offA, int offB, int bS) {
+  const int qpav = (qp_p + qp_q + 1) >> 1;
+  const int ia = min(max(qpav + offA, 0), 51), ib = min(max(qpav + offB, 0), 51);
+  Thr t;
+  t.alpha = (int)wv::lds_u8(ldsBase + T_ALPHA + ia);
+  t.beta = (int)wv::lds_u8(ldsBase + T_BETA + ib);
+  t.tc0 = (int)wv::lds_u8(ldsBase + T_TCB + 64 * (min(max(bS, 1), 3) - 1) + ia);
+  return t;
+}
+// bS of segment seg of edge E in direction DIR of a dryv_bs_rec (four 4-bit values per 16-bit word)
+template <int DIR, int E>
+WV int bs_of(const u32x4 rec, int seg) {
+  const unsigned w = DIR ? (E < 2 ? rec.z : rec.w) : (E < 2 ? rec.x : rec.y);
+  return (int)((w >> (16 * (E & 1) + 4 * seg)) & 15u);
+}
 WV int iabs(int v) { return v < 0 ? -v : v; }
 
-// One line of samples across an edge (8.7.2.3 / 8.7.2.4). STRONG: bS = 4, else bS = 3. `on`: this lane's edge is filtered at all.
+// One line of samples across an edge (8.7.2.3 / 8.7.2.4). STRONG: bS = 4, else bS < 4 with t.tc0 of that bS. `on`: this lane's edge is filtered at all.
 template <bool STRONG, bool CHROMA>
 WV void filter_line(int& p3, int& p2, int& p1, int& p0, int& q0, int& q1, int& q2, int& q3, const Thr t, bool on) {
   on = on && iabs(p0 - q0) < t.alpha && iabs(p1 - p0) < t.beta && iabs(q1 - q0) < t.beta;  // filterSamplesFlag
@@ -138,7 +171,9 @@ WV void unpack4(unsigned w, int v[4]) {
 WV unsigned pack4(const int v[4]) { return (unsigned)v[0] | ((unsigned)v[1] << 8) | ((unsigned)v[2] << 16) | ((unsigned)v[3] << 24); }
 
 // One wave: claims bands of its plane kind until none are left. ldsBase: the workgroup's tables; ts: this wave's scratch.
-template <bool LUMA>
+// BSREC: strengths from A.bs and quantisers from A.recs (a macroblock edge takes the bS-4 form and then the bS < 4 form, each
+// enabled per lane by its segment's bS: at most one of them changes a line); otherwise 4 / 3 and dryv_mb_desc.
+template <bool LUMA, bool BSREC = false>
 WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const int ts) {
   const int lane0 = wv::lane_id();
   const int W = P.W, H = P.H, nF = P.n_frames;
@@ -179,12 +214,20 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
     u32x4 rowY = {0, 0, 0, 0};
     u32x2 rowC = {0, 0};
     unsigned dCur = 0, dTop = 0;
+    u32x4 bsRec = {0, 0, 0, 0};
     auto prefetch = [&](int x) {
       if (rowOk && x >= 0 && x < W) {
         if (LUMA) rowY = wv::ld_u128_a2(plane + (size_t)(16 * r + i) * pitchY + 16 * x);
         else rowC = *(const u32x2*)(plane + (cpl ? offCr : offCb) + (size_t)(8 * r + crow) * pitchC + 8 * x);
-        dCur = *(const unsigned*)(mbsF + (size_t)r * W + x);
-        if (mbB) dTop = *(const unsigned*)(mbsF + (size_t)(r - 1) * W + x);
+        if (BSREC) {
+          const size_t a = ((size_t)f * H + r) * W + x;
+          dCur = *(const unsigned*)(A.recs + a * A.recStride);
+          if (mbB) dTop = *(const unsigned*)(A.recs + (a - W) * A.recStride);
+          bsRec = A.bs[a];
+        } else {
+          dCur = *(const unsigned*)(mbsF + (size_t)r * W + x);
+          if (mbB) dTop = *(const unsigned*)(mbsF + (size_t)(r - 1) * W + x);
+        }
       }
     };
     prefetch(-2 * g);
@@ -202,8 +245,10 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
       const bool fin = rowOk && x >= 1 && x <= W;         // ... and finalises macroblock x - 1
       const int slot = x & 1, other = slot ^ 1;
       const bool mbA = x > 0;
-      const int qp = (int)(dCur >> 24), qpT = (int)(dTop >> 24);
+      const int qp = BSREC ? min((int)((dCur >> 8) & 0xffu), 51) : (int)(dCur >> 24);
+      const int qpT = BSREC ? min((int)((dTop >> 8) & 0xffu), 51) : (int)(dTop >> 24);
       const bool t8 = (dCur & 0xffu) == 1u;
+      const u32x4 bs = bsRec;
       const u32x4 curY = rowY;
       const u32x2 curC = rowC;
 
@@ -300,12 +345,24 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
         unpack4(curY.y, q[1]);
         unpack4(curY.z, q[2]);
         unpack4(curY.w, q[3]);
-        const Thr tE = thresholds(ldsBase, qpLeft, qp, P.offA, P.offB), tI = thresholds(ldsBase, qp, qp, P.offA, P.offB);
-        filter_line<true, false>(p[0], p[1], p[2], p[3], q[0][0], q[0][1], q[0][2], q[0][3], tE, mbA);
+        if (BSREC) {
+          const int seg = i >> 2, b0 = bs_of<0, 0>(bs, seg);
+          const int bI[4] = {0, bs_of<0, 1>(bs, seg), bs_of<0, 2>(bs, seg), bs_of<0, 3>(bs, seg)};
+          const Thr tE = thresholds_bs(ldsBase, qpLeft, qp, P.offA, P.offB, b0);
+          filter_line<true, false>(p[0], p[1], p[2], p[3], q[0][0], q[0][1], q[0][2], q[0][3], tE, mbA && b0 == 4);
+          filter_line<false, false>(p[0], p[1], p[2], p[3], q[0][0], q[0][1], q[0][2], q[0][3], tE, mbA && b0 != 0 && b0 < 4);
 #pragma unroll
-        for (int e = 1; e < 4; e++)
-          filter_line<false, false>(q[e - 1][0], q[e - 1][1], q[e - 1][2], q[e - 1][3], q[e][0], q[e][1], q[e][2], q[e][3], tI,
-                                    !(t8 && (e & 1)));
+          for (int e = 1; e < 4; e++)
+            filter_line<false, false>(q[e - 1][0], q[e - 1][1], q[e - 1][2], q[e - 1][3], q[e][0], q[e][1], q[e][2], q[e][3],
+                                      thresholds_bs(ldsBase, qp, qp, P.offA, P.offB, bI[e]), bI[e] != 0);
+        } else {
+          const Thr tE = thresholds(ldsBase, qpLeft, qp, P.offA, P.offB), tI = thresholds(ldsBase, qp, qp, P.offA, P.offB);
+          filter_line<true, false>(p[0], p[1], p[2], p[3], q[0][0], q[0][1], q[0][2], q[0][3], tE, mbA);
+#pragma unroll
+          for (int e = 1; e < 4; e++)
+            filter_line<false, false>(q[e - 1][0], q[e - 1][1], q[e - 1][2], q[e - 1][3], q[e][0], q[e][1], q[e][2], q[e][3], tI,
+                                      !(t8 && (e & 1)));
+        }
         if (mbA) wv::lds_st32(rowB + 16 * other + 12, pack4(p));
 #pragma unroll
         for (int e = 0; e < 4; e++) wv::lds_st32(rowB + 16 * slot + 4 * e, pack4(q[e]));
@@ -318,9 +375,17 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
         unpack4(wv::lds_u32(crowB + 8 * other + 4), cp);
         unpack4(curC.x, c0);
         unpack4(curC.y, c1);
-        const Thr cE = thresholds(ldsBase, qcL, qc, P.offA, P.offB), cI = thresholds(ldsBase, qc, qc, P.offA, P.offB);
-        filter_line<true, true>(cp[0], cp[1], cp[2], cp[3], c0[0], c0[1], c0[2], c0[3], cE, mbA);
-        filter_line<false, true>(c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3], cI, true);
+        if (BSREC) {  // chroma line k of an edge: luma segment k >> 1; the chroma edge at 4: luma edge 8
+          const int seg = crow >> 1, b0 = bs_of<0, 0>(bs, seg), b2 = bs_of<0, 2>(bs, seg);
+          const Thr cE = thresholds_bs(ldsBase, qcL, qc, P.offA, P.offB, b0), cI = thresholds_bs(ldsBase, qc, qc, P.offA, P.offB, b2);
+          filter_line<true, true>(cp[0], cp[1], cp[2], cp[3], c0[0], c0[1], c0[2], c0[3], cE, mbA && b0 == 4);
+          filter_line<false, true>(cp[0], cp[1], cp[2], cp[3], c0[0], c0[1], c0[2], c0[3], cE, mbA && b0 != 0 && b0 < 4);
+          filter_line<false, true>(c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3], cI, b2 != 0);
+        } else {
+          const Thr cE = thresholds(ldsBase, qcL, qc, P.offA, P.offB), cI = thresholds(ldsBase, qc, qc, P.offA, P.offB);
+          filter_line<true, true>(cp[0], cp[1], cp[2], cp[3], c0[0], c0[1], c0[2], c0[3], cE, mbA);
+          filter_line<false, true>(c0[0], c0[1], c0[2], c0[3], c1[0], c1[1], c1[2], c1[3], cI, true);
+        }
         if (mbA) wv::lds_st32(crowB + 8 * other + 4, pack4(cp));
         wv::lds_st32(crowB + 8 * slot, pack4(c0));
         wv::lds_st32(crowB + 8 * slot + 4, pack4(c1));
@@ -333,12 +398,24 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
         int v[20];
 #pragma unroll
         for (int j = 0; j < 20; j++) v[j] = (int)wv::lds_u8(colB + LSTR * j);
-        const Thr tE = thresholds(ldsBase, qpT, qp, P.offA, P.offB), tI = thresholds(ldsBase, qp, qp, P.offA, P.offB);
-        filter_line<true, false>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], tE, mbB);
+        if (BSREC) {
+          const int seg = i >> 2, b0 = bs_of<1, 0>(bs, seg);
+          const int bI[4] = {0, bs_of<1, 1>(bs, seg), bs_of<1, 2>(bs, seg), bs_of<1, 3>(bs, seg)};
+          const Thr tE = thresholds_bs(ldsBase, qpT, qp, P.offA, P.offB, b0);
+          filter_line<true, false>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], tE, mbB && b0 == 4);
+          filter_line<false, false>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], tE, mbB && b0 != 0 && b0 < 4);
 #pragma unroll
-        for (int e = 1; e < 4; e++)
-          filter_line<false, false>(v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3], v[4 * e + 4], v[4 * e + 5], v[4 * e + 6],
-                                    v[4 * e + 7], tI, !(t8 && (e & 1)));
+          for (int e = 1; e < 4; e++)
+            filter_line<false, false>(v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3], v[4 * e + 4], v[4 * e + 5], v[4 * e + 6],
+                                      v[4 * e + 7], thresholds_bs(ldsBase, qp, qp, P.offA, P.offB, bI[e]), bI[e] != 0);
+        } else {
+          const Thr tE = thresholds(ldsBase, qpT, qp, P.offA, P.offB), tI = thresholds(ldsBase, qp, qp, P.offA, P.offB);
+          filter_line<true, false>(v[0], v[1], v[2], v[3], v[4], v[5], v[6], v[7], tE, mbB);
+#pragma unroll
+          for (int e = 1; e < 4; e++)
+            filter_line<false, false>(v[4 * e], v[4 * e + 1], v[4 * e + 2], v[4 * e + 3], v[4 * e + 4], v[4 * e + 5], v[4 * e + 6],
+                                      v[4 * e + 7], tI, !(t8 && (e & 1)));
+        }
 #pragma unroll
         for (int j = 1; j < 18; j++)
           if (j >= 4 || mbB) wv::lds_st8(colB + LSTR * j, (unsigned)v[j]);
@@ -350,9 +427,17 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
         int c[10], dmy0 = 0, dmy1 = 0;
 #pragma unroll
         for (int j = 0; j < 10; j++) c[j] = (int)wv::lds_u8(ccolB + CSTR * j);
-        const Thr cE = thresholds(ldsBase, qcT, qc, P.offA, P.offB), cI = thresholds(ldsBase, qc, qc, P.offA, P.offB);
-        filter_line<true, true>(dmy0, dmy1, c[0], c[1], c[2], c[3], dmy0, dmy1, cE, mbB);
-        filter_line<false, true>(dmy0, dmy1, c[4], c[5], c[6], c[7], dmy0, dmy1, cI, true);
+        if (BSREC) {
+          const int seg = crow >> 1, b0 = bs_of<1, 0>(bs, seg), b2 = bs_of<1, 2>(bs, seg);
+          const Thr cE = thresholds_bs(ldsBase, qcT, qc, P.offA, P.offB, b0), cI = thresholds_bs(ldsBase, qc, qc, P.offA, P.offB, b2);
+          filter_line<true, true>(dmy0, dmy1, c[0], c[1], c[2], c[3], dmy0, dmy1, cE, mbB && b0 == 4);
+          filter_line<false, true>(dmy0, dmy1, c[0], c[1], c[2], c[3], dmy0, dmy1, cE, mbB && b0 != 0 && b0 < 4);
+          filter_line<false, true>(dmy0, dmy1, c[4], c[5], c[6], c[7], dmy0, dmy1, cI, b2 != 0);
+        } else {
+          const Thr cE = thresholds(ldsBase, qcT, qc, P.offA, P.offB), cI = thresholds(ldsBase, qc, qc, P.offA, P.offB);
+          filter_line<true, true>(dmy0, dmy1, c[0], c[1], c[2], c[3], dmy0, dmy1, cE, mbB);
+          filter_line<false, true>(dmy0, dmy1, c[4], c[5], c[6], c[7], dmy0, dmy1, cI, true);
+        }
         if (mbB) wv::lds_st8(ccolB + CSTR * 1, (unsigned)c[1]);
         wv::lds_st8(ccolB + CSTR * 2, (unsigned)c[2]);
         wv::lds_st8(ccolB + CSTR * 5, (unsigned)c[5]);
@@ -411,6 +496,10 @@ WV void deblock_wave(const DParams& P, const Args& A, const int ldsBase, const i
       } else {
         rowC.x = (unsigned)wv::opaque((int)rowC.x); rowC.y = (unsigned)wv::opaque((int)rowC.y);
         topCn.x = (unsigned)wv::opaque((int)topCn.x); topCn.y = (unsigned)wv::opaque((int)topCn.y);
+      }
+      if (BSREC) {
+        bsRec.x = (unsigned)wv::opaque((int)bsRec.x); bsRec.y = (unsigned)wv::opaque((int)bsRec.y);
+        bsRec.z = (unsigned)wv::opaque((int)bsRec.z); bsRec.w = (unsigned)wv::opaque((int)bsRec.w);
       }
       dCur = (unsigned)wv::opaque((int)dCur);
       dTop = (unsigned)wv::opaque((int)dTop);

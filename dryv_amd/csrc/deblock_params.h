@@ -37,6 +37,11 @@ inline int build_dparams(const dryv_frame_params* fp, const dryv_deblock_params*
   memcpy(P->alpha, ALPHA, 52);
   memcpy(P->beta, BETA, 52);
   memcpy(P->tc0, TC0_BS3, 52);
+  // the bS = 1 and bS = 2 columns from indexA 17 on (below: 0); at every index column 1 <= column 2 <= column 3
+  static const uint8_t TC0_BS1[35] = {0, 0, 0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 4, 5, 6, 6, 7, 8, 9, 10, 11, 13};
+  static const uint8_t TC0_BS2[35] = {0, 0, 0, 0, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 2, 2, 2, 2, 3, 3, 3, 4, 4, 5, 5, 6, 7, 8, 8, 10, 11, 12, 13, 15, 17};
+  memcpy(P->tc0_bs1 + 17, TC0_BS1, 35);
+  memcpy(P->tc0_bs2 + 17, TC0_BS2, 35);
   return DRYV_OK;
 }
 

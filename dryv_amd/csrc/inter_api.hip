@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <new>
 
+#include "deblock_params.h"
 #include "inter_launch.h"
 
 using dryv::inter::Args;
@@ -27,7 +28,13 @@ struct dryv_inter_ctx {
     void* h = nullptr;
     void* d = nullptr;
     size_t cap = 0;   // bytes
-  } refs, refs1, weights;
+  } refs, refs1, weights, ids;   // ids: the deblocking call's picture-id tables, [n_frames][2][16] bytes
+  // deblocking workspace, device only, grow-only: [the filter's counters, progress words and side buffers (deblock_params.h)]
+  // [one dryv_bs_rec per macroblock]
+  void* d_dbwork = nullptr;
+  size_t cap_dbwork = 0;
+  hipEvent_t ev_bs_start = nullptr, ev_bs_stop = nullptr;   // the most recent boundary-strength launch's own start and end
+  bool deblock_timed = false;
   int num_cus = 256;
 };
 
@@ -93,7 +100,8 @@ int dryv_inter_create(dryv_inter_ctx** out, int device_ordinal, void* stream) {
   }
   if (hipMalloc((void**)&ctx->d_status, 16) != hipSuccess || hipMemset(ctx->d_status, 0, 16) != hipSuccess ||
       hipHostMalloc((void**)&ctx->h_status, 16, hipHostMallocDefault) != hipSuccess || hipEventCreate(&ctx->ev_start) != hipSuccess ||
-      hipEventCreate(&ctx->ev_stop) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming) != hipSuccess) {
+      hipEventCreate(&ctx->ev_stop) != hipSuccess || hipEventCreate(&ctx->ev_bs_start) != hipSuccess ||
+      hipEventCreate(&ctx->ev_bs_stop) != hipSuccess || hipEventCreateWithFlags(&ctx->ev_tab, hipEventDisableTiming) != hipSuccess) {
     dryv_inter_destroy(ctx);
     return DRYV_E_DEVICE;
   }
@@ -111,6 +119,10 @@ void dryv_inter_destroy(dryv_inter_ctx* ctx) {
   release(ctx->refs);
   release(ctx->refs1);
   release(ctx->weights);
+  release(ctx->ids);
+  if (ctx->d_dbwork) (void)hipFree(ctx->d_dbwork);
+  if (ctx->ev_bs_start) (void)hipEventDestroy(ctx->ev_bs_start);
+  if (ctx->ev_bs_stop) (void)hipEventDestroy(ctx->ev_bs_stop);
   if (ctx->d_status) (void)hipFree(ctx->d_status);
   if (ctx->h_status) (void)hipHostFree(ctx->h_status);
   if (ctx->ev_start) (void)hipEventDestroy(ctx->ev_start);
@@ -194,6 +206,83 @@ int dryv_inter_submit_device_bipred(dryv_inter_ctx* ctx, const dryv_frame_params
   return DRYV_OK;
 }
 
+int dryv_inter_check_deblock(const dryv_frame_params* fp, const dryv_deblock_params* dp, uint32_t n_frames, int bipred,
+                             uint32_t n_refs0, uint32_t n_refs1) {
+  // the matching submit's checks (a P submit has one list), then build_dparams' checks of dp
+  if (!bipred && n_refs1) return DRYV_E_INVALID;
+  int st = dryv::inter::build_bparams(fp, n_frames, n_refs0, n_refs1, nullptr, nullptr);
+  if (st != DRYV_OK) return st;
+  dryv::deblock::DParams DP;
+  int skip = 0;
+  return dryv::deblock::build_dparams(fp, dp, n_frames, &DP, &skip);
+}
+
+int dryv_inter_deblock_device(dryv_inter_ctx* ctx, const dryv_frame_params* fp, const dryv_deblock_params* dp, uint32_t n_frames,
+                              int bipred, uint32_t n_refs0, uint32_t n_refs1, const void* const* d_refs0, const void* const* d_refs1,
+                              const void* d_mbs, const void* d_coeffs, void* d_yuv, void* d_bs_out) {
+  if (!ctx || !d_refs0 || (n_refs1 && !d_refs1) || !d_mbs || !d_coeffs || !d_yuv) return DRYV_E_INVALID;
+  int st = dryv_inter_check_deblock(fp, dp, n_frames, bipred, n_refs0, n_refs1);
+  if (st != DRYV_OK) return st;
+  IParams P;
+  dryv::deblock::DParams DP;
+  int skip = 0;
+  (void)dryv::inter::build_iparams(fp, n_frames, n_refs0, &P);
+  (void)dryv::deblock::build_dparams(fp, dp, n_frames, &DP, &skip);
+  if (((uintptr_t)d_mbs | (uintptr_t)d_coeffs | (uintptr_t)d_yuv | (uintptr_t)d_bs_out) & 15u) return DRYV_E_INVALID;
+  const size_t n0 = (size_t)n_frames * n_refs0, n1 = (size_t)n_frames * n_refs1;
+  if (!refs_ok(d_refs0, n0) || !refs_ok(d_refs1, n1)) return DRYV_E_INVALID;
+  if (skip) return DRYV_OK;  // disable_deblocking_filter_idc = 1
+  (void)hipSetDevice(ctx->device);
+  const size_t idBytes = (size_t)n_frames * 32, wsBytes = (dryv::deblock::workspace_bytes(DP) + 255) & ~(size_t)255;
+  if ((st = ensure(ctx, ctx->ids, idBytes)) != DRYV_OK) return st;
+  if (ctx->cap_dbwork < wsBytes + (size_t)P.n_mbs * 16) {
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) return DRYV_E_DEVICE;   // (launches in flight may still use the old one)
+    if (ctx->d_dbwork) (void)hipFree(ctx->d_dbwork);
+    ctx->d_dbwork = nullptr;
+    ctx->cap_dbwork = 0;
+    if (hipMalloc(&ctx->d_dbwork, wsBytes + (size_t)P.n_mbs * 16) != hipSuccess) return DRYV_E_NOMEM;
+    ctx->cap_dbwork = wsBytes + (size_t)P.n_mbs * 16;
+  }
+  if (ctx->tab_pending && hipEventSynchronize(ctx->ev_tab) != hipSuccess) return DRYV_E_DEVICE;
+  // picture ids: position (list * 16 + refIdx) of the first entry of the picture's two tables with the same pointer
+  uint8_t* ids = (uint8_t*)ctx->ids.h;
+  memset(ids, 0xFF, idBytes);
+  for (uint32_t f = 0; f < n_frames; f++) {
+    const void* tab[32] = {};
+    for (uint32_t k = 0; k < n_refs0; k++) tab[k] = d_refs0[(size_t)f * n_refs0 + k];
+    for (uint32_t k = 0; k < n_refs1; k++) tab[16 + k] = d_refs1[(size_t)f * n_refs1 + k];
+    for (int k = 0; k < 32; k++)
+      if (tab[k]) ids[f * 32 + k] = (uint8_t)(std::find(tab, tab + 32, tab[k]) - tab);
+  }
+  if (hipMemcpyAsync(ctx->ids.d, ctx->ids.h, idBytes, hipMemcpyHostToDevice, ctx->stream) != hipSuccess ||
+      hipEventRecord(ctx->ev_tab, ctx->stream) != hipSuccess)
+    return DRYV_E_DEVICE;
+  ctx->tab_pending = true;
+  if (hipMemsetAsync(ctx->d_dbwork, 0, dryv::deblock::reset_bytes(DP), ctx->stream) != hipSuccess) return DRYV_E_DEVICE;
+  void* d_bs = (unsigned char*)ctx->d_dbwork + wsBytes;
+  if (dryv::inter::deblock_bs_launch(P, bipred != 0, d_mbs, d_coeffs, ctx->ids.d, d_bs, d_bs_out, ctx->stream, ctx->ev_bs_start,
+                                     ctx->ev_bs_stop) != hipSuccess)
+    return DRYV_E_DEVICE;
+  // the whole resident grid, capped at one wave per band and plane kind
+  const int wpb = dryv::inter::inter_deblock_waves_per_block();
+  const long long bands = (long long)n_frames * ((DP.H + 3) / 4);
+  const int grid = (int)std::max(1ll, std::min((long long)ctx->num_cus * dryv::inter::inter_deblock_blocks_per_cu(), (2 * bands + wpb - 1) / wpb));
+  if (dryv::inter::inter_deblock_launch(DP, d_mbs, bipred ? 144u : 80u, d_bs, d_yuv, ctx->d_status, ctx->d_dbwork, grid, ctx->stream,
+                                        ctx->ev_start, ctx->ev_stop) != hipSuccess)
+    return DRYV_E_DEVICE;
+  ctx->timed = ctx->deblock_timed = true;
+  return DRYV_OK;
+}
+
+int dryv_inter_last_deblock_ms(dryv_inter_ctx* ctx, float* bs_ms, float* filter_ms) {
+  if (!ctx || !bs_ms || !filter_ms) return DRYV_E_INVALID;
+  if (!ctx->deblock_timed) return DRYV_E_STATE;
+  if (hipEventSynchronize(ctx->ev_stop) != hipSuccess || hipEventElapsedTime(bs_ms, ctx->ev_bs_start, ctx->ev_bs_stop) != hipSuccess ||
+      hipEventElapsedTime(filter_ms, ctx->ev_start, ctx->ev_stop) != hipSuccess)
+    return DRYV_E_DEVICE;
+  return DRYV_OK;
+}
+
 int dryv_inter_sync(dryv_inter_ctx* ctx) {
   if (!ctx) return DRYV_E_INVALID;
   (void)hipSetDevice(ctx->device);
@@ -202,6 +291,7 @@ int dryv_inter_sync(dryv_inter_ctx* ctx) {
       hipMemsetAsync(ctx->d_status, 0, 16, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
     return DRYV_E_DEVICE;
   ctx->tab_pending = false;
+  if (*ctx->h_status & 4u) return DRYV_E_DEVICE;   // a band of the deblocking filter gave up waiting for the band above
   return (*ctx->h_status & 1u) ? DRYV_E_UNSUPPORTED : DRYV_OK;
 }
 

@@ -262,6 +262,36 @@ class InterContext:
                                                          tabs[1][1], None if w is None else w.ctypes.data, C.c_void_p(d_mbs),
                                                          C.c_void_p(d_coeffs), C.c_void_p(d_yuv_out)))
 
+    def deblock_device(self, fp, dp, n_frames, bipred, refs0, refs1, d_mbs, d_coeffs, d_yuv, d_bs_out=None, return_bs=False):
+        """In-loop deblocking (H.264 8.7) of n_frames pictures at d_yuv, in place, behind the submit that wrote them: the same
+        records (bipred: abi.INTER_BMB_DTYPE, else abi.INTER_MB_DTYPE), coefficients and reference tables as that submit. d_bs_out:
+        a raw device pointer to n_mbs * 16 bytes that receive the abi.BS_REC_DTYPE records. return_bs: the records come back as a
+        numpy array instead (allocated through torch; this waits: sync() has then run, with allow_unsupported)."""
+        tabs = []
+        for refs in (refs0, refs1 or [[] for _ in range(int(n_frames))]):
+            flat = [int(p) for per_frame in refs for p in per_frame]
+            n = len(flat) // int(n_frames) if n_frames else 0
+            if n * int(n_frames) != len(flat) or any(len(r) != n for r in refs):
+                raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
+            tabs.append((n, (C.c_void_p * max(len(flat), 1))(*flat)))
+        buf = None
+        if return_bs:
+            import torch
+            buf = torch.zeros(int(n_frames) * fp.pic_width_in_mbs * fp.pic_height_in_mbs * 16, dtype=torch.uint8, device="cuda")
+            d_bs_out = buf.data_ptr()
+        _check(self._lib.dryv_inter_deblock_device(self._h, C.byref(fp), C.byref(dp), int(n_frames), int(bool(bipred)), tabs[0][0],
+                                                   tabs[1][0], tabs[0][1], tabs[1][1], C.c_void_p(d_mbs), C.c_void_p(d_coeffs),
+                                                   C.c_void_p(d_yuv), C.c_void_p(d_bs_out)))
+        if buf is not None:
+            self.sync(allow_unsupported=True)
+            return buf.cpu().numpy().view(abi.BS_REC_DTYPE)
+
+    def last_deblock_ms(self):
+        """(boundary-strength kernel, filter kernel) device times of the most recent deblock_device, in ms."""
+        a, b = C.c_float(), C.c_float()
+        _check(self._lib.dryv_inter_last_deblock_ms(self._h, C.byref(a), C.byref(b)))
+        return float(a.value), float(b.value)
+
     def sync(self, allow_unsupported=False):
         st = self._lib.dryv_inter_sync(self._h)
         if not (allow_unsupported and st == abi.DRYV_E_UNSUPPORTED):

@@ -179,7 +179,7 @@ int dryv_recon_wait_packed(dryv_recon_ctx *ctx, const dryv_output_desc *od, uint
 
 /* ---- in-loop deblocking filter ---------------------------------------------------------------------------
  * ITU-T H.264 clause 8.7 for this library's domain (frame macroblocks, 4:2:0, 8 bit, one slice per picture, all macroblocks
- * intra). dryv parses the syntax elements below (slice/header.rs:609-640) and does not filter (README.md:15 unchecked): there
+ * intra; the inter stage's P and B pictures: dryv_inter_deblock_device). dryv parses the syntax elements below (slice/header.rs:609-640) and does not filter (README.md:15 unchecked): there
  * is no reference behaviour to be equal to, and reconstruction's default output stays unfiltered, as dryv's is. */
 typedef struct {
   uint8_t disable_deblocking_filter_idc; /* 0 filter every edge, 1 none, 2 = 0 for one slice per picture */
@@ -223,8 +223,8 @@ void *dryv_recon_stream(dryv_recon_ctx *ctx);
  *
  * Not done here, by the caller instead: motion-vector prediction and P_Skip inference (records carry final vectors; a skipped
  * macroblock is one vector on all 16 blocks plus flag bit1). B macroblocks and weighted prediction: dryv_inter_submit_device_bipred
- * below. Not supported: field / MBAFF, intra macroblocks inside P pictures (mb_type != 0: status bit, DRYV_E_UNSUPPORTED at sync, the
- * macroblock zero-filled), deblocking of inter edges.
+ * below. In-loop deblocking of the stage's pictures: dryv_inter_deblock_device below. Not supported: field / MBAFF, intra macroblocks
+ * inside P pictures (mb_type != 0: status bit, DRYV_E_UNSUPPORTED at sync, the macroblock zero-filled).
  *
  * Reference pictures: each a full coded picture in this library's own output layout (dryv_recon_frame_bytes), 16-byte aligned.
  * Vectors may point anywhere; samples outside the picture are the nearest edge sample (8.4.2.2's coordinate clipping). An
@@ -261,7 +261,8 @@ void dryv_inter_destroy(dryv_inter_ctx *ctx);
 int dryv_inter_submit_device(dryv_inter_ctx *ctx, const dryv_frame_params *fp, uint32_t n_frames, uint32_t n_refs,
                              const void *const *d_refs, const void *d_mbs, const void *d_coeffs, void *d_yuv_out);
 /* Waits for everything submitted: DRYV_OK, DRYV_E_UNSUPPORTED (a record with mb_type != 0, qp > 51 or a ref_idx outside
- * 0..n_refs-1 since the last sync: those macroblocks are zero-filled, the others are reconstructed) or DRYV_E_DEVICE. */
+ * 0..n_refs-1 since the last sync: those macroblocks are zero-filled, the others are reconstructed) or DRYV_E_DEVICE (a HIP
+ * error, or a band of dryv_inter_deblock_device's filter that gave up waiting for the band above). */
 int dryv_inter_sync(dryv_inter_ctx *ctx);
 /* Device time of the most recent launch (the dispatch's own start and end). Valid after dryv_inter_sync. */
 int dryv_inter_last_kernel_ms(dryv_inter_ctx *ctx, float *ms);
@@ -281,8 +282,7 @@ int dryv_inter_last_kernel_ms(dryv_inter_ctx *ctx, float *ms);
  *   implicit, two lists:                           w 64 - w1, w1   rnd 32                            sh 6          off 0
  *
  * Still the caller's: direct and skip vector derivation (spatial or temporal), reference list construction, the implicit
- * weights from POC distances, intra macroblocks in B pictures (reported and zero-filled), field / MBAFF, deblocking of inter
- * edges. */
+ * weights from POC distances, intra macroblocks in B pictures (reported and zero-filled), field / MBAFF. */
 typedef struct dryv_inter_bmb {  /* 144 bytes, raster order, frames concatenated */
   uint8_t mb_type;               /* 0 = inter. Anything else: unsupported, zero-filled */
   uint8_t qp;                    /* QPY 0..51 (above: unsupported) */
@@ -317,6 +317,48 @@ int dryv_inter_submit_device_bipred(dryv_inter_ctx *ctx, const dryv_frame_params
                                     const void *const *d_refs0, const void *const *d_refs1,
                                     const dryv_inter_weights *weights,
                                     const void *d_mbs, const void *d_coeffs, void *d_yuv_out);
+
+/* ---- inter prediction stage: in-loop deblocking of P and B pictures ----------------------------------------------------------
+ * ITU-T H.264 clause 8.7 for the pictures this stage writes: the filtered picture is what the next P or B picture predicts from, so
+ * I -> P / B -> reference -> P / B stays on the device. Two kernels per call: the boundary strengths (8.7.2.1) of every 4-sample
+ * edge segment from coefficients, reference pictures and vectors, then the band filter of dryv_recon_deblock_device driven by
+ * them (bS 0..4 per segment, tC0 of table 8-17's column for that bS, qp from the inter records).
+ *
+ * bS of the segment between block p (left or above) and block q, first match: 0 on the left edge of picture column 0 and the top
+ * edge of picture row 0; 0 on the edges at 4 and 12 of a macroblock with flag bit0 (transform 8x8 edges are not filtered); 4 on a
+ * macroblock edge and 3 inside if either macroblock has mb_type != 0; 2 if either block (under flag bit0: its 8x8 quadrant) has a
+ * non-zero luma coefficient (a slot under flag bit1 is not read and counts as zero; chroma never counts); 1 if the blocks use
+ * different reference PICTURES (device pointers are compared, not indices) or a different number of vectors; 1 if a component of
+ * the vectors that belong to the same picture differs by 4 or more quarter samples (two vectors on one picture each: unless
+ * either pairing passes entirely); otherwise 0.
+ *
+ * Stays out: field / MBAFF edges, several slices per picture (disable_deblocking_filter_idc 2 filters as 0; per-slice offsets),
+ * and intra macroblocks' PIXELS in P / B pictures, which the inter stage still zero-fills (their edges get bS 4 / 3 all the same). */
+typedef struct dryv_bs_rec { uint8_t v[2][4][2]; } dryv_bs_rec;   /* 16 bytes per macroblock */
+/* v[dir][edge]: dir 0 = vertical edges (left macroblock edge, then x = 4, 8, 12), dir 1 = horizontal edges (top, y = 4, 8, 12);
+ * two bytes = four 4-bit bS values, segment k (the four luma lines 4k..4k+3 along the edge) in bits 4k..4k+3 of the
+ * little-endian 16-bit word. 0 = not filtered. Chroma line k of an edge takes luma segment k >> 1; the chroma edge at 4 takes
+ * luma edge 8. */
+
+/* The checks of the matching submit (bipred 0: dryv_inter_check with n_refs0, and n_refs1 must be 0; bipred 1:
+ * dryv_inter_check_bipred) plus dp's ranges (dryv_recon_deblock_device's); no device needed. */
+int dryv_inter_check_deblock(const dryv_frame_params *fp, const dryv_deblock_params *dp, uint32_t n_frames,
+                             int bipred, uint32_t n_refs0, uint32_t n_refs1);
+/* Filters n_frames pictures at d_yuv in place, ordered on the stage's stream like the submits (so it may follow the submit that
+ * writes d_yuv without a sync between) and reported through dryv_inter_sync. It needs what produced the pictures: the same
+ * records (bipred 0: dryv_inter_mb, 1: dryv_inter_bmb), coefficient buffer and reference tables (HOST arrays, copied before the
+ * call returns; d_refs1 may be NULL when n_refs1 is 0). d_bs_out: NULL, or n_mbs * 16 bytes of device memory that receive the
+ * dryv_bs_rec records, for the caller to keep or inspect. Alignment as the submits (d_bs_out too).
+ * disable_deblocking_filter_idc == 1: DRYV_OK and nothing is launched. */
+int dryv_inter_deblock_device(dryv_inter_ctx *ctx, const dryv_frame_params *fp, const dryv_deblock_params *dp,
+                              uint32_t n_frames, int bipred /* 0: dryv_inter_mb records, 1: dryv_inter_bmb */,
+                              uint32_t n_refs0, uint32_t n_refs1,
+                              const void *const *d_refs0, const void *const *d_refs1,
+                              const void *d_mbs, const void *d_coeffs, void *d_yuv /* filtered in place */,
+                              void *d_bs_out /* NULL, or n_mbs * 16 bytes: the bS records, for the caller to keep or inspect */);
+/* Device times of the most recent dryv_inter_deblock_device: the boundary-strength kernel's and the filter's (each dispatch's
+ * own start and end; dryv_inter_last_kernel_ms then reports the filter's). Valid after dryv_inter_sync. */
+int dryv_inter_last_deblock_ms(dryv_inter_ctx *ctx, float *bs_ms, float *filter_ms);
 
 const char *dryv_recon_strerror(int status);
 const char *dryv_recon_last_device_error(dryv_recon_ctx *ctx);

@@ -10,7 +10,12 @@ restatement of the standard in tests/test_inter.py. usage: inter_rate.py [frames
 picture f's I picture, list 1 picture f + 1's; both lists' vectors have the P run's statistics; every quadrant draws L0 / L1 /
 both with a third each; default weights. Records both kernel times and their ratio (expected: below 2, since residual and
 output are shared) and checks the top of the first B picture against tests/test_inter_bipred.py. Default --out:
-profiles/inter_rate_bipred.json."""
+profiles/inter_rate_bipred.json.
+
+--deblock: after the P run, in the same process, dryv_inter_deblock_device on that P batch: the device times of the boundary-
+strength kernel and of the band filter separately (the stage's events), then the intra deblocking stage on the reconstructed I
+pictures (what tools/deblock_rate.py measures), for comparison. Checks the top macroblock rows of the first filtered P picture and
+its bS records against tests/test_inter_deblock.py. Default --out: profiles/inter_deblock_rate.json."""
 import json
 import os
 import sys
@@ -72,9 +77,10 @@ def main():
     import torch
     from test_inter import reference
     frames = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 300
-    bipred = "--bipred" in sys.argv
+    bipred, deblock = "--bipred" in sys.argv, "--deblock" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else (
-        os.path.join(ROOT, "profiles", "inter_rate_bipred.json") if bipred else None)
+        os.path.join(ROOT, "profiles", "inter_rate_bipred.json") if bipred else
+        os.path.join(ROOT, "profiles", "inter_deblock_rate.json") if deblock else None)
     fp, imbs, ico, n = synth.workload("C2_1080p_intra_4x4", n_frames=frames)
     per = fp.pic_width_in_mbs * fp.pic_height_in_mbs
     mbs, co = p_pictures(per, np.random.default_rng(12))
@@ -95,6 +101,26 @@ def main():
             d_b = torch.zeros(n * per * 384, dtype=torch.uint8, device="cuda")
             refs1 = [[d_i.data_ptr() + ((f + 1) % n) * per * 384] for f in range(n)]
             btimes = timed(ictx, lambda: ictx.submit_device_bipred(fp, n, refs, refs1, None, d_bm.data_ptr(), d_c.data_ptr(), d_b.data_ptr()))
+        if deblock:
+            dp = abi.make_deblock_params(0, 0, 0)
+            unfiltered, d_bs = d_p.clone(), torch.zeros(n * per * 16, dtype=torch.uint8, device="cuda")
+            dtimes = []
+            for rep in range(12):
+                d_p.copy_(unfiltered)
+                torch.cuda.synchronize()
+                ictx.deblock_device(fp, dp, n, False, refs, None, d_m.data_ptr(), d_c.data_ptr(), d_p.data_ptr(), d_bs.data_ptr())
+                ictx.sync()
+                if rep >= 2:
+                    dtimes.append(ictx.last_deblock_ms())
+            filtered, d_p = d_p, unfiltered
+            itimes = []
+            for rep in range(12):
+                d_f = d_i.clone()
+                torch.cuda.synchronize()
+                rctx.deblock_device(fp, dp, n, d_im.data_ptr(), d_f.data_ptr())
+                rctx.sync()
+                if rep >= 2:
+                    itimes.append(rctx.last_kernel_ms())
     ms = float(np.mean(times))
     st, want = reference(fp, 1, [[d_i[:per * 384].cpu().numpy()]], mbs[:per], co[:per])
     ok = bool(st == 0 and np.array_equal(d_p[:per * 384].cpu().numpy(), want))
@@ -125,6 +151,32 @@ def main():
         print("bipred: %.3f ms per %d frames = %.2f x the P batch of this session (expected below 2); first picture == reference: %s"
               % (bms, n, bms / ms, bok))
         assert bok
+    if deblock:
+        import test_inter_deblock as tid
+        # (the top three macroblock rows as a picture of their own, compared on the top two: no filtered sample of those depends
+        # on the third row's bottom edge)
+        W, H, R = fp.pic_width_in_mbs, fp.pic_height_in_mbs, 3
+        top = lambda pic, rows: np.concatenate([pic[:256 * W * rows], pic[256 * W * H:256 * W * H + 64 * W * rows],
+                                                pic[320 * W * H:320 * W * H + 64 * W * rows]])
+        fpc = abi.FrameParams.from_buffer_copy(fp)
+        fpc.pic_height_in_mbs = R
+        bs = tid.bs_reference(W, R, mbs[:W * R], co[:W * R], ([[0]], [[]]))
+        want = tid.deblock_reference(fpc, dp, 1, mbs[:W * R], top(d_p[:per * 384].cpu().numpy(), R), bs)
+        cut = lambda pic: np.concatenate([pic[:256 * W * 2], pic[256 * W * R:256 * W * R + 64 * W * 2], pic[320 * W * R:320 * W * R + 64 * W * 2]])
+        dok = bool(np.array_equal(cut(top(filtered[:per * 384].cpu().numpy(), R)), cut(want)) and
+                   np.array_equal(d_bs[:W * 2 * 16].cpu().numpy().view(np.uint16).reshape(-1, 2, 4), tid.words(bs)[:W * 2]))
+        a_ms, b_ms, i_ms = float(np.mean([t[0] for t in dtimes])), float(np.mean([t[1] for t in dtimes])), float(np.mean(itimes))
+        hist = np.bincount((d_bs.cpu().numpy()[:, None] >> np.array([0, 4]) & 15).reshape(-1), minlength=5)
+        res = {"frames": n, "p": res, "deblock": {
+            "bs_kernel_ms_avg": a_ms, "bs_kernel_ms_min": float(np.min([t[0] for t in dtimes])),
+            "filter_kernel_ms_avg": b_ms, "filter_kernel_ms_min": float(np.min([t[1] for t in dtimes])),
+            "bs_share_of_segments": {str(k): float(v) / hist.sum() for k, v in enumerate(hist)},
+            "first_picture_matches_restatement": dok},
+            "intra_deblock": {"kernel_ms_avg": i_ms, "kernel_ms_min": float(np.min(itimes))},
+            "filter_over_intra": b_ms / i_ms, "expected": "near 1: the same picture bytes plus 16 bytes per macroblock"}
+        print("deblock of the P batch: bS kernel %.3f ms, filter %.3f ms; intra deblocking of the I batch %.3f ms: filter / intra = %.2f; "
+              "first picture == restatement: %s" % (a_ms, b_ms, i_ms, b_ms / i_ms, dok))
+        assert dok
     if out_path:
         json.dump(res, open(out_path, "w"), indent=1)
 
