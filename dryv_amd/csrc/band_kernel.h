@@ -938,14 +938,20 @@ WV void team_wait_ge(int addr, unsigned want) {
 
 constexpr int HAND_WORDS = 16;   // dwords per macroblock of the hand-off records (Args::handoff)
 // The hand-off record of a macroblock of the band above: four lanes (li = 0..3) read one 8-byte granule each, {four pixels,
-// tag} (luma: the bottom line's four quarters; chroma: Cb, Cb, Cr, Cr). `v`: what the lanes requested a step ago (or just
-// now). Polls -- the lanes whose tag is not there yet again -- until every tag is (bounded: see SPIN_LIMIT).
-WV unsigned long long await_granules(const unsigned long long* rec, unsigned long long v, bool fetchLane, unsigned tag, unsigned* status,
-                                     unsigned task, int s, int lane) {
+// tag} (luma: the bottom line's four quarters; chroma: Cb, Cb, Cr, Cr). A granule is requested a step before it is looked at
+// and from the second round of a team's tasks on its tag is there at the first look: the look is straight-line code, the
+// poll a path of its own, so that no register of the poll is in flight (and nothing waits for one) anywhere else.
+WV bool granules_there(unsigned long long v, bool fetchLane, unsigned tag) { return !wv::any(fetchLane && (unsigned)(v >> 32) != tag); }
+// The cold path behind a first look that found a tag missing: the lanes whose tag is not there request their granule again
+// until every tag is (bounded: see SPIN_LIMIT). Every request is looked at (waited for) inside the loop: the path leaves
+// nothing of its own in flight.
+WV unsigned long long poll_granules(const unsigned long long* rec, unsigned long long v, bool fetchLane, unsigned tag, unsigned* status,
+                                    unsigned task, int s, int lane) {
   unsigned spins = 0;
-  while (wv::any(fetchLane && (unsigned)(v >> 32) != tag)) {
+  do {
     wv::sleep_short();
     if (fetchLane && (unsigned)(v >> 32) != tag) v = wv::ld_sc1_64(rec);
+    v = wv::opaque64(v);   // (waited for here, by every lane and on every way out of the loop)
     if (++spins > SPIN_LIMIT) {
       // every spin is bounded: a band above that never gets there is reported (status bit 2 + where), not waited for
       if (lane == 0) {
@@ -956,7 +962,7 @@ WV unsigned long long await_granules(const unsigned long long* rec, unsigned lon
       }
       break;
     }
-  }
+  } while (!granules_there(v, fetchLane, tag));
   return v;
 }
 
@@ -1462,17 +1468,32 @@ WV void band_front(const KParams& P, const Args& A, const int ldsBase, const int
       if (needUp && !EXP_SKIP(2)) {
         const unsigned long long* const rec = (const unsigned long long*)handUp + ((HAND_WORDS / 2) * mbx + li);
         unsigned long long g64 = 0;
-        if (fetchLane) g64 = (s > 0 && lane < 16) ? lineN : wv::ld_sc1_64(rec);
-        g64 = await_granules(rec, g64, fetchLane, A.gen, A.status, task, s, lane);
+        if (s == 0) {
+          // a band's first step: nothing was requested ahead (lanes 16..19 fetch here and nowhere else)
+          if (fetchLane) g64 = wv::ld_sc1_64(rec);
+          g64 = wv::opaque64(g64);   // (waited for on this path, not where it joins the other)
+        } else {
+          WV_MARK("front.look.begin");
+          if (fetchLane) g64 = lineN;   // (s > 0: the fetch lanes are lanes 0..3)
+          WV_MARK("front.look.end");
+        }
+        if (__builtin_expect(!granules_there(g64, fetchLane, A.gen), 0)) g64 = poll_granules(rec, g64, fetchLane, A.gen, A.status, task, s, lane);
         lineV = (unsigned)g64;
+        WV_MARK("front.request.begin");
         if (lane < 4 && s + 2 < W) lineN = wv::ld_sc1_64(rec + HAND_WORDS / 2);
+        WV_MARK("front.request.end");
       }
+      WV_MARK("front.prefetch.begin");
       if (HAS_I8 || EXP_SKIP(0) || EXP_DUP_IS(0)) load_coefs_luma(s + 1, kN1);  // (otherwise: requested inside the residual pass)
+      WV_MARK("front.prefetch.end");
       PH(3);  // hand-off traffic, coefficient prefetch
 
       // ---- the step's record for BACK: residuals [blkIdx][y][x], table rows, kinds. The buffer is free once BACK has
       // finished the step two back.
+      WV_MARK("front.free.begin");
       if (gstep >= (unsigned)NBUF) team_wait(ts + S_FLAGS + F_FREE + 4 * buf, gstep - NBUF + 1);
+      WV_MARK("front.free.end");
+      WV_MARK("front.record.begin");
       if (!(HAS_I8 && kind == 1)) {   // (an Intra8x8 macroblock's residuals: BACK8's)
         const int dst = ts + S_RES + RES_BUF * buf + hResOff;
         wv::lds_st128(dst, u32x4{rA[0], rA[1], rA[2], rA[3]});
@@ -1498,6 +1519,7 @@ WV void band_front(const KParams& P, const Args& A, const int ldsBase, const int
       }
       wv::wave_sync();
       if (lane == 0) wv::lds_st32(ts + S_FLAGS + F_READY + 4 * buf, gstep + 1);  // the record is complete
+      WV_MARK("front.record.end");
       PH(4);  // record for BACK
     }
     if (!claimedNext) nextTask = claim_push(seq + 1);
@@ -1602,6 +1624,13 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
 #pragma unroll
     for (int k = 0; k < 8; k++) rB[k] = 0;
     load_coefs_chroma(0);
+    // The prologue's loads are waited for here, once per task. Left in flight into the step loop they are "pending" at its
+    // header for good, as the compiler sees it, and it then waits in every even step, straight behind the granule request
+    // of that step, for everything the wave has in flight: the request itself and the pixel-row stores of the step before.
+    kN1 = (unsigned)wv::opaque((int)kN1);
+    cB0 = u32x4{(unsigned)wv::opaque((int)cB0.x), (unsigned)wv::opaque((int)cB0.y), (unsigned)wv::opaque((int)cB0.z), (unsigned)wv::opaque((int)cB0.w)};
+    cB1 = u32x4{(unsigned)wv::opaque((int)cB1.x), (unsigned)wv::opaque((int)cB1.y), (unsigned)wv::opaque((int)cB1.z), (unsigned)wv::opaque((int)cB1.w)};
+    dcB = wv::opaque(dcB);
     PH(0);  // task, prologue loads
     unsigned long long lineN = 0;   // this lane's granule of the band above's hand-off record of macroblock s+1, requested during the previous step
 
@@ -1647,10 +1676,21 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
       if (needUp && !EXP_SKIP(9)) {
         const unsigned long long* const rec = (const unsigned long long*)handUp + ((HAND_WORDS / 2) * mbx + 4 + li);
         unsigned long long g64 = 0;
-        if (fetchLane) g64 = (s > 0 && lane < 16) ? lineN : wv::ld_sc1_64(rec);
-        g64 = await_granules(rec, g64, fetchLane, A.gen, A.status, task, s, lane);
+        if (s == 0) {
+          // a band's first step: nothing was requested ahead (lanes 16..19 fetch here and nowhere else)
+          if (fetchLane) g64 = wv::ld_sc1_64(rec);
+          g64 = wv::opaque64(g64);   // (waited for on this path, not where it joins the other)
+        } else {
+          WV_MARK("chroma.look.begin");
+          // (no wait: lineN was waited for in the step that requested it, in front of that step's stores: below)
+          if (fetchLane) g64 = lineN;   // (s > 0: the fetch lanes are lanes 0..3)
+          WV_MARK("chroma.look.end");
+        }
+        if (__builtin_expect(!granules_there(g64, fetchLane, A.gen), 0)) g64 = poll_granules(rec, g64, fetchLane, A.gen, A.status, task, s, lane);
         lineV = (unsigned)g64;
+        WV_MARK("chroma.request.begin");
         if (lane < 4 && s + 2 < W) lineN = wv::ld_sc1_64(rec + HAND_WORDS / 2);
+        WV_MARK("chroma.request.end");
       }
       PH(1);  // hand-off traffic
 
@@ -1693,8 +1733,10 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
         for (int k = 0; k < 4; k++) wv::swap32(rB[k], rB[k + 4]);
         dEven = dOdd = dC;
         wv::swap32(dEven, dOdd);
+        WV_MARK("chroma.prefetch.begin");
         load_coefs_chroma(s + 2);
         kN1 = load_kind(s + 2);
+        WV_MARK("chroma.prefetch.end");
       }
       if (fetchLane) wv::lds_st32(ts + S_RINGC + RINGC_ENT * (mbx & 3) + 4 * li, lineV);
       wv::wave_sync();
@@ -1797,8 +1839,15 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
       // to be acknowledged when the chip is busy. (Measured alternative, not kept: a constant number of stores per step,
       // padded with stores to a dump area, so that the compiler could count them: its waits stayed vmcnt(0) across the
       // loop back-edge and the batch took longer.)
+      WV_MARK("chroma.settle.begin");
       kN1 = (unsigned)wv::opaque((int)kN1);
       cB0.x = (unsigned)wv::opaque((int)cB0.x); cB1.x = (unsigned)wv::opaque((int)cB1.x); dcB = wv::opaque(dcB);
+      // The granule requested at the top of this step is "used" here as well, a prediction pass behind its request and
+      // for the same reason: the look at the top of the next step then needs no wait at all, where any wait would also be
+      // one for the stores below (one counter for loads and stores, and the compiler does not count across the two kinds).
+      lineN = wv::opaque64(lineN);
+      WV_MARK("chroma.settle.end");
+      WV_MARK("chroma.stores.begin");
       // bottom chroma lines for the row below (ring) or the band below (write-through): lanes 0..1 of row g Cb, 2..3 Cr
       EXP_REP(12) {
         unsigned v = 0;
@@ -1854,6 +1903,7 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
         }
       }
       wv::wave_sync();
+      WV_MARK("chroma.stores.end");
       PH(4);  // chroma lines, copies, flush
     }
     TLE(task, 2, TNOW());

@@ -169,6 +169,8 @@ WV void wait_vm(int n) {
     default: asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); break;
   }
 }
+// an inert assembly comment that names a region of the kernel for tools/handoff_waits.py
+#define WV_MARK(name) asm volatile("; @mark " name)
 #ifndef DRYV_BAND_SLEEP
 #define DRYV_BAND_SLEEP 4  // s_sleep argument (x64 clocks) between two polls of a progress word
 #endif
@@ -189,9 +191,18 @@ template <int P>
 WV void setprio() { __builtin_amdgcn_s_setprio(P); }
 // the value, behind a barrier the optimiser cannot see through: what is derived from it is recomputed, not kept live
 WV int opaque(int v) { asm volatile("" : "+v"(v)); return v; }
+WV unsigned long long opaque64(unsigned long long v) { asm volatile("" : "+v"(v)); return v; }
 // a use of v the optimiser cannot remove (the loaded value of a cache-warming load: the load stays, its wait lands here)
 WV void consume(unsigned v) { asm volatile("" : : "v"(v)); }
 
 }  // namespace wv
 
 #endif  // DRYV_WAVE_IMPL
+
+#ifdef DRYV_EMU
+// The host lane emulator (tests/emu) brings the rest of the interface itself; these follow the device definitions above.
+namespace wv {
+static inline unsigned long long opaque64(unsigned long long v) { return v; }
+}  // namespace wv
+#define WV_MARK(name) ((void)0)
+#endif
