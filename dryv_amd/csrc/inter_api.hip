@@ -7,6 +7,7 @@
 
 #include "deblock_params.h"
 #include "inter_launch.h"
+#include "status_words.h"
 
 using dryv::inter::Args;
 using dryv::inter::BArgs;
@@ -291,8 +292,8 @@ int dryv_inter_sync(dryv_inter_ctx* ctx) {
       hipMemsetAsync(ctx->d_status, 0, 16, ctx->stream) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess)
     return DRYV_E_DEVICE;
   ctx->tab_pending = false;
-  if (*ctx->h_status & 4u) return DRYV_E_DEVICE;   // a band of the deblocking filter gave up waiting for the band above
-  return (*ctx->h_status & 1u) ? DRYV_E_UNSUPPORTED : DRYV_OK;
+  if (*ctx->h_status & dryv::kStatusGaveUp) return DRYV_E_DEVICE;   // (a band of the deblocking filter)
+  return (*ctx->h_status & dryv::kStatusUnsupported) ? DRYV_E_UNSUPPORTED : DRYV_OK;
 }
 
 int dryv_inter_last_kernel_ms(dryv_inter_ctx* ctx, float* ms) {

@@ -186,6 +186,18 @@ def test_error_behaviour(recon_ctx):
     assert e.value.status == abi.DRYV_E_INVALID
     lib = abi.load_library()
     assert lib.dryv_recon_wait(recon_ctx._h, co.ctypes.data, 10) == abi.DRYV_E_STATE  # wait without submit
+    # sync() on a host submit leaves it waitable, once
+    st, want = oracle.reconstruct(fp, 1, mbs, co)
+    assert st == 0
+    out = np.empty(want.size, dtype=np.uint8)
+    recon_ctx.submit(fp, 1, mbs, co)
+    recon_ctx.sync()
+    assert np.array_equal(recon_ctx.wait(), want)
+    assert lib.dryv_recon_wait(recon_ctx._h, out.ctypes.data, out.size) == abi.DRYV_E_STATE
+    # a buffer one byte short is refused and the batch stays in flight: a full-size wait still delivers it
+    recon_ctx.submit(fp, 1, mbs, co)
+    assert lib.dryv_recon_wait(recon_ctx._h, out.ctypes.data, out.size - 1) == abi.DRYV_E_INVALID
+    assert np.array_equal(recon_ctx.wait(), want)
     assert_parity(recon_ctx, fp, 1, mbs, co)  # the context still works
 
 
