@@ -231,14 +231,19 @@ class InterContext:
     def __exit__(self, *a):
         self.close()
 
+    @staticmethod
+    def _ref_table(refs, n_frames):
+        """(n_refs, ctypes table) of n_frames sequences of n_refs raw device pointers."""
+        flat = [int(p) for per_frame in refs for p in per_frame]
+        n = len(flat) // int(n_frames) if n_frames else 0
+        if n * int(n_frames) != len(flat) or any(len(r) != n for r in refs):
+            raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
+        return n, (C.c_void_p * max(len(flat), 1))(*flat)
+
     def submit_device(self, fp, n_frames, refs, d_mbs, d_coeffs, d_yuv_out):
         """refs: n_frames sequences of n_refs raw device pointers (reference pictures in the output layout); the other three
         are raw device pointers: abi.INTER_MB_DTYPE records, int16 (n_mbs, 384), the output pictures. Completes at sync()."""
-        flat = [int(p) for per_frame in refs for p in per_frame]
-        n_refs = len(flat) // int(n_frames) if n_frames else 0
-        if n_refs * int(n_frames) != len(flat) or any(len(r) != n_refs for r in refs):
-            raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
-        tab = (C.c_void_p * max(len(flat), 1))(*flat)
+        n_refs, tab = self._ref_table(refs, n_frames)
         _check(self._lib.dryv_inter_submit_device(self._h, C.byref(fp), int(n_frames), n_refs, tab, C.c_void_p(d_mbs),
                                                   C.c_void_p(d_coeffs), C.c_void_p(d_yuv_out)))
 
@@ -246,13 +251,7 @@ class InterContext:
         """The two-list entry point (B pictures, weighted prediction). refs0 / refs1: n_frames sequences of n_refs0 / n_refs1 raw
         device pointers (refs1 may be empty sequences: weighted-P pictures); weights: an abi.INTER_WEIGHTS_DTYPE array of n_frames
         entries, or None (default prediction); d_mbs: abi.INTER_BMB_DTYPE records; the rest as submit_device."""
-        tabs = []
-        for refs in (refs0, refs1):
-            flat = [int(p) for per_frame in refs for p in per_frame]
-            n = len(flat) // int(n_frames) if n_frames else 0
-            if n * int(n_frames) != len(flat) or any(len(r) != n for r in refs):
-                raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
-            tabs.append((n, (C.c_void_p * max(len(flat), 1))(*flat)))
+        tabs = [self._ref_table(refs, n_frames) for refs in (refs0, refs1)]
         w = None
         if weights is not None:
             w = np.ascontiguousarray(weights, dtype=abi.INTER_WEIGHTS_DTYPE).reshape(-1)
@@ -267,13 +266,7 @@ class InterContext:
         records (bipred: abi.INTER_BMB_DTYPE, else abi.INTER_MB_DTYPE), coefficients and reference tables as that submit. d_bs_out:
         a raw device pointer to n_mbs * 16 bytes that receive the abi.BS_REC_DTYPE records. return_bs: the records come back as a
         numpy array instead (allocated through torch; this waits: sync() has then run, with allow_unsupported)."""
-        tabs = []
-        for refs in (refs0, refs1 or [[] for _ in range(int(n_frames))]):
-            flat = [int(p) for per_frame in refs for p in per_frame]
-            n = len(flat) // int(n_frames) if n_frames else 0
-            if n * int(n_frames) != len(flat) or any(len(r) != n for r in refs):
-                raise ReconError(abi.DRYV_E_INVALID, "refs must be n_frames lists of equal length")
-            tabs.append((n, (C.c_void_p * max(len(flat), 1))(*flat)))
+        tabs = [self._ref_table(refs, n_frames) for refs in (refs0, refs1 or [[] for _ in range(int(n_frames))])]
         buf = None
         if return_bs:
             import torch

@@ -139,7 +139,7 @@ def test_deblock_on_gpu(recon_ctx, geo):
 def test_host_path_with_deblocking_and_packing(recon_ctx):
     """dryv_recon_submit + dryv_recon_wait_filtered: reconstruction, deblocking and the output stage chained on the device,
     only the wanted bytes copied back: equal to oracle reconstruction -> oracle deblocking -> cropping in numpy."""
-    from test_recon_gpu import _expected_packed
+    from util import expected_packed
     W, H, frames = 12, 9, 2
     fp = abi.make_frame_params(W, H)
     mbs, co = synth.generate(fp, synth.config(i4x4=0.6, i8x8=0.0, qp=(20, 48)), 808, 0, frames)
@@ -149,7 +149,7 @@ def test_host_path_with_deblocking_and_packing(recon_ctx):
     for od, crop in ((None, (0, 0, 0, 0)), (abi.make_output_desc(abi.OUT_NV12, (2, 0, 0, 8)), (2, 0, 0, 8))):
         recon_ctx.submit(fp, frames, mbs, co)
         got = recon_ctx.wait_filtered(dp, od)
-        want = filt if od is None else _expected_packed(filt, W, H, frames, abi.OUT_NV12, crop)
+        want = filt if od is None else expected_packed(filt, W, H, frames, abi.OUT_NV12, crop)
         assert np.array_equal(got, want)
     recon_ctx.submit(fp, frames, mbs, co)
     assert np.array_equal(recon_ctx.wait_filtered(None, None), yuv)     # no stage: the plain pictures

@@ -10,34 +10,14 @@ import pytest
 
 import oracle
 from dryv_amd import abi
-from util import make_coeffs, make_mb, split_planes
+from util import build_frame_kat, check_luma, kat_mb, make_coeffs, make_mb, split_planes
 
 with open(os.path.join(os.path.dirname(__file__), "golden", "kat_vectors.json")) as f:
     KAT = json.load(f)["vectors"]
 
 
-def _mbrec(d):
-    return make_mb(kind=d["kind"], qp=d["qp"], i16=d["i16"], chroma=d["chroma"], prev=d["prev"], rem=d["rem"])
-
-
 FRAME_KATS = [v for v in KAT if "mbs" in v]
 SINGLE_KATS = [v for v in KAT if v.get("kind") == "single_mb"]
-
-
-def build_frame_kat(v):
-    fp = abi.make_frame_params(v["W"], v["H"], transform_8x8=True)
-    mbs = np.array([_mbrec(m) for m in v["mbs"]], dtype=abi.MB_DESC_DTYPE)
-    co = np.stack([make_coeffs(m["coeffs"]) for m in v["mbs"]])
-    return fp, mbs, co
-
-
-def check_luma(Y, expect):
-    if "Y" in expect:
-        assert np.all(Y == expect["Y"]), Y
-    else:  # one value per 8x8 quadrant of a single macroblock: top-left, top-right, bottom-left, bottom-right
-        q = expect["Yq"]
-        assert np.all(Y[:8, :8] == q[0]) and np.all(Y[:8, 8:] == q[1]), Y
-        assert np.all(Y[8:, :8] == q[2]) and np.all(Y[8:, 8:] == q[3]), Y
 
 
 @pytest.mark.parametrize("v", FRAME_KATS, ids=[v["name"] for v in FRAME_KATS])
@@ -63,7 +43,7 @@ def build_single_kat(v):
     if "Cb_bottom_row" in nb:
         Cb[7, :8] = nb["Cb_bottom_row"]
     kinds = np.full(W * H, nb["kind"], dtype=np.uint8)
-    return fp, yuv, kinds, _mbrec(v["mb"]), make_coeffs(v["mb"]["coeffs"])
+    return fp, yuv, kinds, kat_mb(v["mb"]), make_coeffs(v["mb"]["coeffs"])
 
 
 @pytest.mark.parametrize("v", SINGLE_KATS, ids=[v["name"] for v in SINGLE_KATS])

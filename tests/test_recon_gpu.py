@@ -13,7 +13,8 @@ import pytest
 
 import oracle
 from dryv_amd import abi, synth, Frame, ReconError
-from util import first_mismatch, make_coeffs, make_mb, split_planes, packed16_bound_batches, packed16_8x8_bound_batches
+from util import (build_frame_kat, check_luma, expected_packed, first_mismatch, make_coeffs, make_mb, split_planes, packed16_bound_batches,
+                  packed16_8x8_bound_batches)
 
 pytestmark = pytest.mark.gpu
 
@@ -37,7 +38,6 @@ FRAME_KATS = [v for v in KAT if "mbs" in v]
 
 @pytest.mark.parametrize("v", FRAME_KATS, ids=[v["name"] for v in FRAME_KATS])
 def test_kat_on_gpu(recon_ctx, v):
-    from test_oracle_kat import build_frame_kat, check_luma
     fp, mbs, co = build_frame_kat(v)
     yuv = recon_ctx.reconstruct(fp, 1, mbs, co)
     Y, Cb, Cr = split_planes(yuv, v["W"], v["H"])
@@ -657,24 +657,6 @@ def test_pipelined_host_path_chunk_boundaries(recon_ctx):
             recon_ctx.free_host(a)
 
 
-def _expected_packed(yuv, W, H, frames, fmt, crop):
-    """The output stage restated in numpy: crop the oracle's full planes, then I420 or NV12 byte order."""
-    l, r, t, b = crop
-    out = []
-    per = W * H * 384
-    for f in range(frames):
-        Y, Cb, Cr = split_planes(yuv[f * per:(f + 1) * per], W, H)
-        Y = Y[t:16 * H - b, l:16 * W - r]
-        Cb = Cb[t // 2:8 * H - b // 2, l // 2:8 * W - r // 2]
-        Cr = Cr[t // 2:8 * H - b // 2, l // 2:8 * W - r // 2]
-        out.append(Y.reshape(-1))
-        if fmt == abi.OUT_NV12:
-            out.append(np.stack([Cb, Cr], axis=-1).reshape(-1))
-        else:
-            out += [Cb.reshape(-1), Cr.reshape(-1)]
-    return np.concatenate(out)
-
-
 @pytest.mark.parametrize("geo", [(7, 5, 2, (0, 0, 0, 0)), (7, 5, 2, (2, 6, 4, 10)), (12, 9, 1, (0, 0, 0, 8)),
                                  (3, 2, 3, (14, 16, 2, 0)), (1, 1, 1, (0, 2, 0, 2)), (20, 4, 1, (6, 0, 30, 0))])
 def test_output_stage_crop_and_nv12(recon_ctx, geo):
@@ -689,7 +671,7 @@ def test_output_stage_crop_and_nv12(recon_ctx, geo):
     assert st == 0
     for fmt in (abi.OUT_I420, abi.OUT_NV12):
         od = abi.make_output_desc(fmt, crop)
-        want = _expected_packed(full, W, H, frames, fmt, crop)
+        want = expected_packed(full, W, H, frames, fmt, crop)
         recon_ctx.submit(fp, frames, mbs, co)
         got = recon_ctx.wait_packed(od)
         assert got.size == want.size and np.array_equal(got, want), (fmt, int(np.flatnonzero(got != want)[0]))

@@ -1,7 +1,9 @@
-"""Helpers shared by the tests: building macroblock records by hand, plane views."""
+"""Helpers shared by the tests: building macroblock records by hand, plane views, the inter stage's input generators and fixture."""
 import numpy as np
+import pytest
 
 from dryv_amd import abi
+from oracle import spec_model as sm
 
 
 def make_mb(kind=2, qp=26, i16=2, chroma=0, prev=0, rem=None, nz=0xFFFF):
@@ -34,6 +36,45 @@ def split_planes(yuv, W, H, frame=0):
     nl, nc = 256 * W * H, 64 * W * H
     return (f[:nl].reshape(16 * H, 16 * W), f[nl:nl + nc].reshape(8 * H, 8 * W),
             f[nl + nc:].reshape(8 * H, 8 * W))
+
+
+def kat_mb(d):
+    """A macroblock entry of tests/golden/kat_vectors.json as a record."""
+    return make_mb(kind=d["kind"], qp=d["qp"], i16=d["i16"], chroma=d["chroma"], prev=d["prev"], rem=d["rem"])
+
+
+def build_frame_kat(v):
+    fp = abi.make_frame_params(v["W"], v["H"], transform_8x8=True)
+    mbs = np.array([kat_mb(m) for m in v["mbs"]], dtype=abi.MB_DESC_DTYPE)
+    co = np.stack([make_coeffs(m["coeffs"]) for m in v["mbs"]])
+    return fp, mbs, co
+
+
+def check_luma(Y, expect):
+    if "Y" in expect:
+        assert np.all(Y == expect["Y"]), Y
+    else:  # one value per 8x8 quadrant of a single macroblock: top-left, top-right, bottom-left, bottom-right
+        q = expect["Yq"]
+        assert np.all(Y[:8, :8] == q[0]) and np.all(Y[:8, 8:] == q[1]), Y
+        assert np.all(Y[8:, :8] == q[2]) and np.all(Y[8:, 8:] == q[3]), Y
+
+
+def expected_packed(yuv, W, H, frames, fmt, crop):
+    """The output stage restated in numpy: crop the oracle's full planes, then I420 or NV12 byte order."""
+    l, r, t, b = crop
+    out = []
+    per = W * H * 384
+    for f in range(frames):
+        Y, Cb, Cr = split_planes(yuv[f * per:(f + 1) * per], W, H)
+        Y = Y[t:16 * H - b, l:16 * W - r]
+        Cb = Cb[t // 2:8 * H - b // 2, l // 2:8 * W - r // 2]
+        Cr = Cr[t // 2:8 * H - b // 2, l // 2:8 * W - r // 2]
+        out.append(Y.reshape(-1))
+        if fmt == abi.OUT_NV12:
+            out.append(np.stack([Cb, Cr], axis=-1).reshape(-1))
+        else:
+            out += [Cb.reshape(-1), Cr.reshape(-1)]
+    return np.concatenate(out)
 
 
 def first_mismatch(a, b, W, H):
@@ -155,3 +196,181 @@ def packed16_8x8_bound_batches(fp, synth, frames=1, qps=(0, 7, 17, 24, 29, 30, 3
                             else np.where(np.arange(64) % 2, -1, 1) if sgn == 2 else rng.choice([-1, 1], size=64))
                     co[a, 64 * b:64 * b + 64] = np.clip(blk * sign, -32768, 32767)
             yield qp, bump, mbs, co.astype(np.int16)
+
+
+# ---- the inter stage (test_inter*.py): input generators and the stage fixture; the models they are compared with: oracle.inter_model
+DENOMS = ((0, 5, 7), (7, 0, 3))   # explicit mode: luma / chroma log2 denominators of pictures 0, 1, 2
+
+
+@pytest.fixture(scope="module")
+def inter_ctx():
+    import dryv_amd
+    with dryv_amd.InterContext(0) as ctx:
+        yield ctx
+
+
+# half sample to the right of a 16-sample row repeated down a 1 x 1 picture: (the row, the predicted row)
+P_HALF_ROWS = (([10] * 3 + [50] * 13, [11, 5, 30, 55, 49] + [50] * 11),          # (10 - 50 + 200 + 1000 - 250 + 50 + 16) >> 5 = 30
+               ([0, 0, 255, 255] + [0] * 12, [0, 120, 255, 120, 0, 8] + [0] * 10))   # (10200 + 16) >> 5 = 319 -> 255
+
+
+def make_p_case(W, H, frames, n_refs, mode, t8, qps, span, seed):
+    """Random records / coefficients / reference pictures. span: vector range in luma samples, or "far": beyond the picture.
+    Coefficients are bounded by construction: per 4x4 block two AC entries of at most 10000 / max scaled LevelScale each and
+    a DC share of 10000 (8x8: two entries of 6000 / ...: gain 2.25), so that no value of 8.5.12 - 8.5.13 leaves 16 bits."""
+    rng = np.random.default_rng(seed)
+    lists4, lists8 = rng.integers(8, 21, size=(6, 16)), rng.integers(8, 21, size=(6, 64))
+    fp = abi.make_frame_params(W, H, cqo_cb=int(rng.integers(-6, 7)), cqo_cr=int(rng.integers(-6, 7)), transform_8x8=t8 != "no",
+                               scaling4x4=lists4, scaling8x8=lists8)
+    refs = [[rng.integers(0, 256, size=384 * W * H, dtype=np.uint8) for _ in range(n_refs)] for _ in range(frames)]
+    n = frames * W * H
+    mbs, co = np.zeros(n, dtype=abi.INTER_MB_DTYPE), np.zeros((n, 384), dtype=np.int16)
+    k = 0   # running count of per-block vectors: every luma and chroma fraction occurs by construction
+    for a in range(n):
+        qp = int(rng.integers(qps[0], qps[1] + 1))
+        m = mode if mode != "mixed" else ("uniform", "quadrant", "block")[int(rng.integers(0, 3))]
+        far = lambda: int(rng.integers(200, 4001)) * (1 if rng.random() < 0.5 else -1)
+        vec = lambda: (far(), far()) if span == "far" else tuple(int(v) for v in rng.integers(-4 * span, 4 * span + 1, size=2))
+        if m == "block":
+            for b in range(16):
+                vx, vy = vec()
+                mbs["mv"][a][b] = ((vx & ~7) | (k & 7), (vy & ~7) | ((k >> 3) & 7))
+                k += 1
+        else:
+            v4 = [vec() for _ in range(4)]
+            for b in range(16):
+                mbs["mv"][a][b] = v4[0] if m == "uniform" else v4[b >> 2]
+        one_ref = m == "uniform" and rng.random() < 0.8   # (a single vector over different references: the per-quadrant path)
+        mbs["ref_idx"][a] = int(rng.integers(0, n_refs)) if one_ref else rng.integers(0, n_refs, size=4)
+        use8 = t8 == "yes" or (t8 == "mixed" and rng.random() < 0.5)
+        mbs["qp"][a], mbs["flags"][a] = qp, int(use8)
+        kind = rng.random()
+        if kind < 1 / 3:            # no residual: the slot must not be read
+            mbs["flags"][a] |= 2
+            co[a] = 0x7FFF
+            continue
+        if kind < 0.4:              # a coded macroblock whose coefficients are all zero
+            continue
+        cap4 = lambda q: max(1, (29 * 20) << max(q // 6 - 4, 0) >> max(4 - q // 6, 0))
+        if use8:
+            cmax = min(500, 6000 // max(1, (58 * 20) << max(qp // 6 - 6, 0) >> max(6 - qp // 6, 0)))
+            for q in range(4):
+                co[a, 64 * q + rng.choice(64, size=2, replace=False)] = rng.integers(-cmax, cmax + 1, size=2)
+        else:
+            cmax = min(500, 10000 // cap4(qp))
+            for b in range(16):
+                co[a, 16 * b + rng.choice(16, size=2, replace=False)] = rng.integers(-cmax, cmax + 1, size=2)
+        for pl in range(2):
+            qpc = sm.qp_chroma(qp, (fp.chroma_qp_index_offset, fp.second_chroma_qp_index_offset)[pl])
+            cmax, dmax = min(500, 10000 // cap4(qpc)), min(500, 10000 // (4 * max(1, (18 * 20 << (qpc // 6)) >> 5)))
+            co[a, 256 + 64 * pl:260 + 64 * pl] = rng.integers(-dmax, dmax + 1, size=4)
+            for blk in range(4):
+                co[a, 260 + 64 * pl + 15 * blk + rng.choice(15, size=2, replace=False)] = rng.integers(-cmax, cmax + 1, size=2)
+    return fp, refs, mbs, co
+
+
+def make_b_case(W, H, frames, n0, n1, mode, vectors, t8, seed):
+    """Two P cases of make_p_case (vectors, references; the first one's coefficients and flags) widened into one batch of
+    dryv_inter_bmb records: every quadrant draws L0 / L1 / both, per quadrant or as a 16x8 / 8x16 split (all L0 without list 1,
+    all both on a one-macroblock picture)."""
+    rng = np.random.default_rng(seed)
+    span = "far" if vectors == "far" else 24
+    fp, refs0, p0, co = make_p_case(W, H, frames, n0, "uniform" if vectors == "far" else vectors, t8, (0, 51), span, seed)
+    _, refs1, p1, _ = make_p_case(W, H, frames, max(n1, 1), "uniform" if vectors == "far" else vectors, t8, (0, 51), span, seed + 1)
+    mbs = np.zeros(len(p0), dtype=abi.INTER_BMB_DTYPE)
+    for k in ("qp", "flags"):
+        mbs[k] = p0[k]
+    mbs["mv"][:, 0], mbs["mv"][:, 1] = p0["mv"], p1["mv"]
+    mbs["ref_idx"][:, 0], mbs["ref_idx"][:, 1] = p0["ref_idx"], p1["ref_idx"]
+    for a in range(len(mbs)):
+        d = rng.integers(0, 3, size=4)
+        use = [d[q] for q in ((0, 1, 2, 3), (0, 0, 2, 2), (0, 1, 0, 1))[int(rng.integers(0, 3))]]   # 0 L0, 1 L1, 2 both
+        use = [0] * 4 if n1 == 0 else [2] * 4 if W * H == 1 else use
+        for q in range(4):
+            if use[q] != 2:
+                mbs["ref_idx"][a, 1 - use[q], q] = -1
+    wts = None
+    if mode != "default":
+        wts = np.zeros(frames, dtype=abi.INTER_WEIGHTS_DTYPE)
+        wts["mode"] = 1 if mode == "explicit" else 2
+        for f in range(frames if mode == "explicit" else 0):
+            wts["luma_log2_denom"][f], wts["chroma_log2_denom"][f] = DENOMS[0][f % 3], DENOMS[1][f % 3]
+            w = rng.integers(-128, 128, size=(2, 16, 3))
+            unit = np.array([1 << DENOMS[0][f % 3]] + [1 << DENOMS[1][f % 3]] * 2)
+            wts["expl"]["w"][f] = np.where(rng.random((2, 16, 3)) < 0.25, unit, w)
+            wts["expl"]["o"][f] = rng.integers(-128, 128, size=(2, 16, 3))
+        if mode == "implicit":
+            wts["implicit_w1"] = rng.integers(-64, 129, size=(frames, 16, 16))
+            wts["implicit_w1"][:, 0, 0], wts["implicit_w1"][:, 0, 1 % max(n1, 1)] = -64, 128
+    return fp, refs0, (refs1 if n1 else [[] for _ in range(frames)]), wts, mbs, co
+
+
+# (mode, luma denom, chroma denom, luma w, o, chroma w, o, implicit w1, lists) -> (Y, C) from flat references 200 / 100
+KNOWN = [(0, 0, 0, None, None, None, None, None, (0, 0), (150, 150)),
+         (1, 5, 2, (64, -32), (3, 3), (3, 2), (-5, -6), None, (0, 0), (153, 95)),        # C: (804 >> 3) + (-10 >> 1) = 100 - 5
+         (1, 7, 0, (-128, 127), (127, 127), (1, -1), (-20, -21), None, (0, 0), (77, 30)),  # Y: (-12772 >> 8) + 127; C: (101 >> 1) - 20
+         (1, 0, 3, (0, -1), (0, 10), (0, 20), (0, -7), None, (-1, 0), (0, 243)),          # list 1 only; C: (2004 >> 3) - 7
+         (2, 0, 0, None, None, None, None, 128, (0, 0), (0, 0)),
+         (2, 0, 0, None, None, None, None, -64, (0, 0), (255, 255))]
+
+
+def known_b_case(row):
+    """A row of KNOWN as one B macroblock without residual: (fp, refs0, refs1, weights or None, records, coefficients, (Y, C))."""
+    mode, dl, dc, wl, ol, wc, oc, w1, lists, want = row
+    fp = abi.make_frame_params(1, 1)
+    mbs, co = np.zeros(1, dtype=abi.INTER_BMB_DTYPE), np.zeros((1, 384), dtype=np.int16)
+    mbs["flags"], mbs["qp"], mbs["ref_idx"][0] = 2, 26, np.array(lists)[:, None]
+    wts = np.zeros(1, dtype=abi.INTER_WEIGHTS_DTYPE)
+    wts["mode"], wts["luma_log2_denom"], wts["chroma_log2_denom"] = mode, dl, dc
+    if mode == 1:
+        wts["expl"]["w"][0, :, 0, 0], wts["expl"]["o"][0, :, 0, 0] = wl, ol
+        wts["expl"]["w"][0, :, 0, 1:], wts["expl"]["o"][0, :, 0, 1:] = np.array(wc)[:, None], np.array(oc)[:, None]
+    if mode == 2:
+        wts["implicit_w1"][0, 0, 0] = w1
+    refs = [[np.full(384, v, dtype=np.uint8)] for v in (200, 100)]
+    return fp, [refs[0]], [refs[1]], wts if mode else None, mbs, co, want
+
+
+def _set(m, a, l0=None, l1=None, **kw):   # macroblock a of hand-made B records: list X = (refIdx, vector) on all blocks, or None: unused
+    for X, l in ((0, l0), (1, l1)):
+        m["ref_idx"][a, X], m["mv"][a, X] = (-1, 0) if l is None else l
+    for k, v in kw.items():
+        m[k][a] = v
+
+
+_coef = lambda co, a, pos, v=1: co.__setitem__((a, pos), v)
+# 3 x 2 macroblocks, two frames; pictures A = 0, B = 1; list 0 of frame 0: [A, B, A], of frame 1: [B, A, A]; list 1: [A, B] in both.
+# Every macroblock starts as (L0 index 0, zero vector, no residual). Probes: (macroblock, dir, edge, segment) -> bS; E: macroblock 1's left edge.
+KEYS, E = ([[0, 1, 0], [1, 0, 0]], [[0, 1], [0, 1]]), (1, 0, 0, 0)
+BS_CASES = [("d%s" % (v,), lambda m, c, v=v: _set(m, 1, (0, v)), {E: w}) for v, w in (((3, 0), 0), ((4, 0), 1), ((0, 3), 0), ((0, 4), 1), ((-4, 0), 1), ((-3, -3), 0))] + [
+    ("same-picture-other-index", lambda m, c: (_set(m, 1, (2, (0, 0))), _set(m, 7, (2, (0, 0)))), {E: 0, (7, 0, 0, 0): 1}),
+    ("lists-swapped", lambda m, c: (_set(m, 0, (0, (8, 0)), (1, (-8, 4))), _set(m, 1, (1, (-8, 4)), (0, (8, 0)))), {E: 0}),
+    ("one-picture-cross", lambda m, c: (_set(m, 0, (0, (0, 0)), (0, (20, 0))), _set(m, 1, (2, (20, 0)), (0, (0, 0)))), {E: 0}),
+    ("one-picture-neither", lambda m, c: (_set(m, 0, (0, (0, 0)), (0, (20, 0))), _set(m, 1, (0, (20, 0)), (0, (8, 0)))), {E: 1}),
+    ("one-against-two", lambda m, c: _set(m, 1, (0, (0, 0)), (0, (0, 0))), {E: 1}),
+    ("neighbour-coefficient", lambda m, c: (_set(m, 0, (0, (0, 0)), flags=0), _coef(c, 0, 16 * 5 + 3)), {E: 2, (1, 0, 0, 1): 0, (0, 0, 3, 0): 2}),
+    ("chroma-only", lambda m, c: (_set(m, 1, (0, (0, 0)), flags=0), _coef(c, 1, slice(256, 384), 7)), {E: 0}),
+    # list 2 of 64, an entry in the bytes of block 8: the whole lower-left quadrant, seen from inside and from the macroblock below
+    ("t8-one-entry", lambda m, c: (_set(m, 1, (0, (0, 0)), flags=1), _coef(c, 1, 128 + 5)),
+     {E: 0, (1, 0, 0, 2): 2, (1, 0, 0, 3): 2, (1, 0, 1, 2): 0, (1, 0, 2, 2): 2, (1, 0, 3, 2): 0, (1, 1, 1, 0): 0, (1, 1, 2, 0): 2,
+      (1, 1, 2, 1): 2, (1, 1, 3, 0): 0, (4, 1, 0, 0): 2, (4, 1, 0, 1): 2, (4, 1, 0, 2): 0}),
+    ("no-residual-garbage", lambda m, c: (_set(m, 1, (0, (0, 0)), flags=2), _coef(c, 1, slice(0, 384), 0x7FFF)), {E: 0}),
+    ("intra-neighbour", lambda m, c: _set(m, 1, (0, (0, 0)), mb_type=1), {E: 4, (1, 0, 1, 0): 3, (1, 1, 3, 2): 3, (2, 0, 0, 3): 4, (4, 1, 0, 0): 4}),
+    ("picture-border", lambda m, c: _set(m, 0, (0, (0, 0)), mb_type=1), {(0, 0, 0, 0): 0, (0, 1, 0, 3): 0, (0, 0, 1, 0): 3, (3, 0, 0, 0): 0, (3, 1, 0, 0): 4})]
+
+
+def bs_case(case):
+    """The records and coefficients of a BS_CASES entry: (fp, records, coefficients)."""
+    fp, m, co = abi.make_frame_params(3, 2), np.zeros(12, dtype=abi.INTER_BMB_DTYPE), np.zeros((12, 384), dtype=np.int16)
+    m["qp"], m["flags"], m["ref_idx"][:, 1] = 30, 2, -1
+    case[1](m, co)
+    return fp, m, co
+
+
+def single_list(p):
+    """P records as dryv_inter_bmb records that use list 0 only."""
+    b = np.zeros(len(p), dtype=abi.INTER_BMB_DTYPE)
+    for k in ("mb_type", "qp", "flags"):
+        b[k] = p[k]
+    b["ref_idx"][:, 0], b["ref_idx"][:, 1], b["mv"][:, 0] = p["ref_idx"], -1, p["mv"]
+    return b

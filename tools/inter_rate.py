@@ -4,18 +4,18 @@ picture of the same index (the bench batch, resident in HBM). Random vectors wit
 one vector (half of those without residual: P_Skip), 15 % one per quadrant, 15 % one per 4x4 block. Kernel time from the
 stage's HIP events, macroblocks/s, and the roofline arithmetic of bench.py with 1616 algorithmic bytes per macroblock (80 of
 the record + 768 of coefficients + 384 of the reference read once + 384 written). Checks the first picture against the
-restatement of the standard in tests/test_inter.py. usage: inter_rate.py [frames] [--out file.json]
+restatement of the standard in oracle/inter_model.py (predict_p). usage: inter_rate.py [frames] [--out file.json]
 
 --bipred: after the P run, in the same process, the same number of B pictures through dryv_inter_submit_device_bipred: list 0 is
 picture f's I picture, list 1 picture f + 1's; both lists' vectors have the P run's statistics; every quadrant draws L0 / L1 /
 both with a third each; default weights. Records both kernel times and their ratio (expected: below 2, since residual and
-output are shared) and checks the top of the first B picture against tests/test_inter_bipred.py. Default --out:
+output are shared) and checks the top of the first B picture against oracle.inter_model.predict_b. Default --out:
 profiles/inter_rate_bipred.json.
 
 --deblock: after the P run, in the same process, dryv_inter_deblock_device on that P batch: the device times of the boundary-
 strength kernel and of the band filter separately (the stage's events), then the intra deblocking stage on the reconstructed I
 pictures (what tools/deblock_rate.py measures), for comparison. Checks the top macroblock rows of the first filtered P picture and
-its bS records against tests/test_inter_deblock.py. Default --out: profiles/inter_deblock_rate.json."""
+its bS records against oracle.inter_model's bs_reference and deblock_reference. Default --out: profiles/inter_deblock_rate.json."""
 import json
 import os
 import sys
@@ -24,9 +24,9 @@ import numpy as np
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-sys.path.insert(0, os.path.join(ROOT, "tests"))
 from dryv_amd import abi, synth  # noqa: E402
 from dryv_amd.frame import InterContext, ReconContext  # noqa: E402
+from oracle import inter_model  # noqa: E402
 
 BYTES_PER_MB = 80 + 768 + 384 + 384
 DISTINCT = 10   # pictures' worth of records / coefficients generated on the host; the batch repeats them
@@ -75,7 +75,6 @@ def timed(ictx, submit):
 
 def main():
     import torch
-    from test_inter import reference
     frames = int(sys.argv[1]) if len(sys.argv) > 1 and sys.argv[1].isdigit() else 300
     bipred, deblock = "--bipred" in sys.argv, "--deblock" in sys.argv
     out_path = sys.argv[sys.argv.index("--out") + 1] if "--out" in sys.argv else (
@@ -122,7 +121,7 @@ def main():
                 if rep >= 2:
                     itimes.append(rctx.last_kernel_ms())
     ms = float(np.mean(times))
-    st, want = reference(fp, 1, [[d_i[:per * 384].cpu().numpy()]], mbs[:per], co[:per])
+    st, want = inter_model.predict_p(fp, 1, [[d_i[:per * 384].cpu().numpy()]], mbs[:per], co[:per])
     ok = bool(st == 0 and np.array_equal(d_p[:per * 384].cpu().numpy(), want))
     mbps = n * per / (ms * 1e-3)
     res = {"frames": n, "kernel_ms_avg": ms, "kernel_ms_min": float(np.min(times)), "macroblocks_per_s": mbps,
@@ -132,7 +131,6 @@ def main():
           % (ms, n, mbps / 1e9, mbps * BYTES_PER_MB / 1e9, mbps * BYTES_PER_MB / 8e12, ok))
     assert ok
     if bipred:
-        from test_inter_bipred import reference as b_reference
         # (the reference is three passes of Python ints: the top eight macroblock rows as a picture of their own, compared on the
         # top six, which no vector of +-16 samples takes below the eighth)
         W, H = fp.pic_width_in_mbs, fp.pic_height_in_mbs
@@ -142,7 +140,7 @@ def main():
         fpc = abi.FrameParams.from_buffer_copy(fp)
         fpc.pic_height_in_mbs = R
         pics = [[top(d_i[f * per * 384:(f + 1) * per * 384].cpu().numpy(), H, R)] for f in (0, 1 % n)]
-        st, want = b_reference(fpc, 1, pics[:1], pics[1:], None, bmbs[:W * R], co[:W * R])
+        st, want = inter_model.predict_b(fpc, 1, pics[:1], pics[1:], None, bmbs[:W * R], co[:W * R])
         bok = bool(st == 0 and np.array_equal(top(d_b[:per * 384].cpu().numpy(), H, keep), top(want, R, keep)))
         bms = float(np.mean(btimes))
         res = {"frames": n, "p": res, "bipred": {"kernel_ms_avg": bms, "kernel_ms_min": float(np.min(btimes)),
@@ -152,7 +150,6 @@ def main():
               % (bms, n, bms / ms, bok))
         assert bok
     if deblock:
-        import test_inter_deblock as tid
         # (the top three macroblock rows as a picture of their own, compared on the top two: no filtered sample of those depends
         # on the third row's bottom edge)
         W, H, R = fp.pic_width_in_mbs, fp.pic_height_in_mbs, 3
@@ -160,11 +157,11 @@ def main():
                                                 pic[320 * W * H:320 * W * H + 64 * W * rows]])
         fpc = abi.FrameParams.from_buffer_copy(fp)
         fpc.pic_height_in_mbs = R
-        bs = tid.bs_reference(W, R, mbs[:W * R], co[:W * R], ([[0]], [[]]))
-        want = tid.deblock_reference(fpc, dp, 1, mbs[:W * R], top(d_p[:per * 384].cpu().numpy(), R), bs)
+        bs = inter_model.bs_reference(W, R, mbs[:W * R], co[:W * R], ([[0]], [[]]))
+        want = inter_model.deblock_reference(fpc, dp, 1, mbs[:W * R], top(d_p[:per * 384].cpu().numpy(), R), bs)
         cut = lambda pic: np.concatenate([pic[:256 * W * 2], pic[256 * W * R:256 * W * R + 64 * W * 2], pic[320 * W * R:320 * W * R + 64 * W * 2]])
         dok = bool(np.array_equal(cut(top(filtered[:per * 384].cpu().numpy(), R)), cut(want)) and
-                   np.array_equal(d_bs[:W * 2 * 16].cpu().numpy().view(np.uint16).reshape(-1, 2, 4), tid.words(bs)[:W * 2]))
+                   np.array_equal(d_bs[:W * 2 * 16].cpu().numpy().view(np.uint16).reshape(-1, 2, 4), inter_model.words(bs)[:W * 2]))
         a_ms, b_ms, i_ms = float(np.mean([t[0] for t in dtimes])), float(np.mean([t[1] for t in dtimes])), float(np.mean(itimes))
         hist = np.bincount((d_bs.cpu().numpy()[:, None] >> np.array([0, 4]) & 15).reshape(-1), minlength=5)
         res = {"frames": n, "p": res, "deblock": {
