@@ -1545,7 +1545,7 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
   // Write-out addresses: their lane-dependent parts never change, so they are computed once per kernel and kept (behind an
   // optimisation barrier: the compiler would otherwise rebuild them from the lane id in every step).
   const int hg = lane0 >> 4, hi = lane0 & 15;
-  const int aBot = wv::opaque(ts + S_STC + 16 * CW * hg + 8 * CW * (hi >> 1) + CW * 7 + 4 * (hi & 1));  // + 8 * slot: bottom line of a plane, lanes 0..3
+  const int aBot = wv::opaque(ts + S_STC + 16 * CW * hg + 8 * CW * ((hi & 3) >> 1) + CW * 7 + 4 * (hi & 1));  // + 8 * slot: bottom line of a plane, lanes 0..3 (the others: as lane & 3)
   const int aRing = wv::opaque(ts + S_RINGC + RINGC_ROW * (hg + 1) + 4 * hi);                          // + RINGC_ENT * (x & 3)
   const int aLeftRd = wv::opaque(ts + S_STC + 16 * CW * hg + 8 * CW * (hi >> 3) + CW * (hi & 7) + 7);  // + 8 * slot: column 7
   const int aLeftWr = wv::opaque(ts + S_LEFTC + 16 * hg + 8 * (hi >> 3) + (hi & 7));
@@ -1850,13 +1850,13 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
       WV_MARK("chroma.stores.begin");
       // bottom chroma lines for the row below (ring) or the band below (write-through): lanes 0..1 of row g Cb, 2..3 Cr
       EXP_REP(12) {
-        unsigned v = 0;
-        if (i < 4) v = wv::lds_u32(aBot + 8 * slot);
-        if (valid && i < 4 && g < 3 && g < gl) wv::lds_st32(aRing + RINGC_ENT * (x & 3), v);
-        if (hasBelow && wv::any(valid && g == gl)) {
+        // (every lane reads a dword of the line: no lane mask around the load; the last row's x is wave-uniform: a scalar test)
+        const unsigned v = wv::lds_u32(aBot + 8 * slot);
+        if (valid && i < 4 && g < gl) wv::lds_st32(aRing + RINGC_ENT * (x & 3), v);
+        if (hasBelow && (unsigned)(s - 2 * gl) < (unsigned)W) {
           // the band's last row: a granule {4 pixels, tag} per lane into the hand-off record (lanes 0..3 of the row: Cb, Cb, Cr,
           // Cr), each ONE aligned 8-byte write-through store: the tag arrives with the pixels
-          if (valid && g == gl && i < 4)
+          if (i < 4 && g == gl)
             wv::st_sc1_64((unsigned long long*)handMy + ((HAND_WORDS / 2) * x + 4 + i), (unsigned long long)v | ((unsigned long long)A.gen << 32));
         }
       }
@@ -1867,38 +1867,38 @@ WV void band_chroma(const KParams& P, const Args& A, const int ldsBase, const in
       }
       wv::wave_sync();
       // flush the staged rows: every NSC-th macroblock, or at the end of a row: 8 * NSC contiguous bytes per pixel row.
+      // As in BACK the decision is scalar: a staging group ends on odd steps only, in the rows fg = k0 mod NSC / 2 -- one
+      // candidate at NSC = 8 -- and the row is flushed by all lanes (both planes) without a lane mask; the end of a row
+      // whose width is no multiple of NSC is a path of its own.
       EXP_REP(8)
-      // (scalar pre-test: a row flushes at x = NSC - 1 mod NSC or x = W - 1, and every row's x has the parity of s)
-      if (!EXP_SKIP(8) && ((s & 1) != 0 || ((W - 1 - s) & 1) == 0)) {
-        constexpr int LR = 8 * NSC;  // lanes per macroblock row: 2 planes x 8 pixel rows x NSC / 2 segments of 16 bytes
-#pragma unroll
-        for (int it = 0; it < NSC / 2; it++) {
-          // (64 lanes or more per macroblock row: the row and whether it is flushed at all are wave-uniform, decided on
-          // the scalar side before any lane work)
-          const int fg = LR >= 64 ? (64 * it) / LR : (64 / LR) * it + lane / LR;
-          const int w = LR >= 64 ? ((64 * it) % LR) + lane : lane % LR;
-          const int fx = s - 2 * fg, xp = fx & ~(NSC - 1);
-          const bool rowFlush = fg < nR && fx >= 0 && fx < W && ((fx & (NSC - 1)) == NSC - 1 || fx == W - 1);
-          if (LR >= 64 && !rowFlush) continue;
-          if (LR == 64) {
-            // (everything lane-dependent was prepared before the task loop; the row's part is wave-uniform)
-            const int room = fx - xp;   // macroblocks of the segment in front of fx
-            const bool ok = (fseg2 & 63) <= room;
+      if (!EXP_SKIP(8)) {
+        // (everything lane-dependent was prepared before the task loop; the row's part is wave-uniform. One flush body, in a
+        // loop over the step's candidates -- the rows whose staging group ends, then the row that ends short of one: two
+        // copies of the body cost the builds with the 8x8 transform their scalar-register budget)
+        constexpr int STRIDE = NSC / 2 < 4 ? NSC / 2 : 4, ROWS = 4 / STRIDE;
+        const int k0 = ((s - (NSC - 1)) >> 1) & (STRIDE - 1), e = s - (W - 1);
+#pragma clang loop unroll(disable)
+        for (int c = (s & 1) != 0 ? 0 : ROWS; c <= ROWS; c++) {
+          int fg, xp, room;
+          if (c < ROWS) {
+            fg = k0 + STRIDE * c;
+            xp = s - 2 * fg - (NSC - 1);
+            room = NSC - 1;
+            if (fg >= nR || (unsigned)(xp + NSC - 1) >= (unsigned)W) continue;
+          } else {
+            // row e / 2 is at its last macroblock, and that does not end a staging group
+            if (e < 0 || (e & 1) != 0 || (e >> 1) >= nR || (W & (NSC - 1)) == 0) break;
+            fg = e >> 1;
+            xp = (W - 1) & ~(NSC - 1);
+            room = (W - 1) & (NSC - 1);
+          }
+          {
             const u32x4 v = wv::lds_u128(aFlush + 16 * CW * fg);
             uint8_t* dst = planeY + (oFlush + (unsigned)(8 * (r0 + fg) * pitchC + 8 * xp));
-            if (ok) {
-              if ((fseg2 & 63) + 1 <= room) wv::st_g128(dst, v);
+            if ((FLR >= 64 || lane < FLR) && fseg2 <= room) {
+              if (fseg2 + 1 <= room) wv::st_g128(dst, v);
               else wv::st_g64(dst, u32x2{v.x, v.y});
             }
-            continue;
-          }
-          const int pl = w / (LR / 2), fy = (w / (NSC / 2)) & 7, seg = w % (NSC / 2);
-          const bool ok = rowFlush && xp + 2 * seg <= fx;
-          const u32x4 v = wv::lds_u128(ts + S_STC + 16 * CW * fg + 8 * CW * pl + CW * fy + 16 * seg);
-          uint8_t* dst = planeY + ((pl ? offCr : offCb) + (unsigned)((8 * (r0 + fg) + fy) * pitchC + 8 * xp + 16 * seg));
-          if (ok) {
-            if (xp + 2 * seg + 1 <= fx) wv::st_g128(dst, v);
-            else wv::st_g64(dst, u32x2{v.x, v.y});
           }
         }
       }
@@ -2062,8 +2062,10 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
   uint8_t* planeY = A.yuv;
   unsigned* handMy = A.handoff;   // the band's hand-off records (if it has a band below)
   int par = 0;  // task parity (row 0's luma ring)
-  // flush with 64 lanes per macroblock row (NSY = 4): lane = (pixel row, 16-byte segment)
+  // flush: a macroblock row at a time, lane = (pixel row, 16-byte segment); 64 lanes per pass
+  constexpr int FLR = 16 * NSY, FPASSES = (FLR + 63) / 64;
   const unsigned flushLane = (unsigned)wv::opaque(((lane0 / NSY) & 15) * pitchY + 16 * (lane0 % NSY));
+  const int flushSrc = wv::opaque(ts + S_TILE + TILE_BYTES * ((lane0 % NSY) >> 1) + TILE_STRIDE * (((lane0 / NSY) & 15) + 1) + 8 + 16 * (lane0 & 1));
 
   for (unsigned gstep = 0;; gstep++) {
     const int buf = (int)(gstep % (unsigned)NBUF);
@@ -2153,7 +2155,8 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
       }
       // no macroblock to the left: the left column reads 128 (DC of a block with no neighbour at all: T4R_DC_LEFT; nothing
       // else reads it there)
-      if (wv::any(valid && x == 0 && i4)) {
+      // (row g is at x = 0 in step 2g: nothing to test after step 6)
+      if (s <= 6) {
         if (valid && x == 0 && i4) wv::lds_st8(eG + 4 * E_SLOT * part + E_L3 + 3 - bxp, 128u);
       }
     }
@@ -2210,18 +2213,22 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
         unsigned rr = (unsigned)wv::lds_i16(resS);
         const unsigned dcRounds = (unsigned)wv::rfl((int)wv::lds_u32(ts + S_INFO + 32 * buf + 28));
         constexpr unsigned SEL_DC = 0x0d0d0d0du;   // the selector of the row whose value is the block's DC
-#define I4_BODY(T, DC)                                                                                           \
-        {                                                                                                         \
-          unsigned dcv = 0;                                                                                       \
-          if (DC) {                                                                                               \
+        // One body per round; the DC arithmetic is an addition to it under a wave-uniform test (the mode pre-pass marked the
+        // rounds in which some block of the step takes its own DC). Two whole bodies behind that test cost the wave that paces
+        // the band six scalar instructions a round instead of two.
+#define I4_DCV(T)                                                                                               \
+          if (dcRounds & (1u << (T))) {                                                                           \
             /* DC (pred4x4.rs:116-167) with both neighbours: (L0 + .. + L3 + T0 + .. + T3 + 4) >> 3 of the block's own array */ \
             const u32x4 ee = wv::lds_u128((two ? eB : eG) + offE);                                                \
-            dcv = wv::dot4(ee.x, 0x01000000u, wv::dot4(ee.y, 0x00010101u, wv::dot4(ee.z, 0x01010101u, 4u))) >> 3; \
-          }                                                                                                       \
+            const unsigned dcv = wv::dot4(ee.x, 0x01000000u, wv::dot4(ee.y, 0x00010101u, wv::dot4(ee.z, 0x01010101u, 4u))) >> 3; \
+            pr = en.y == SEL_DC ? dcv * (two ? 0x10001u : 1u) : pr;                                               \
+          }
+#define I4_BODY(T)                                                                                                \
+        {                                                                                                         \
           if (two) {                                                                                              \
             const unsigned pa = wv::perm(hi, lo, en.y), pb = wv::perm(hi, lo, en.z);                              \
             unsigned pr = wv::pk_lshr2(wv::sum4_hi(pb, wv::sum4(pa, 0x00020002u)));                               \
-            if (DC) pr = en.y == SEL_DC ? dcv * 0x10001u : pr;                                                    \
+            I4_DCV(T)                                                                                             \
             const unsigned o = wv::sat_pk_u8(wv::pk_add_sat(pr, rr));                                             \
             if (mine) {                                                                                           \
               const unsigned o8 = o >> 8;                                                                         \
@@ -2233,9 +2240,9 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
             }                                                                                                     \
           } else {                                                                                                \
             const unsigned pq = wv::perm(hi, lo, en.y);                                                           \
-            int pv = (int)(wv::sum4(pq, 2u) >> 2);                                                                \
-            if (DC) pv = en.y == SEL_DC ? (int)dcv : pv;                                                          \
-            const int o = wv::med3(pv + (int)rr, 0, 255);                                                         \
+            unsigned pr = wv::sum4(pq, 2u) >> 2;                                                                  \
+            I4_DCV(T)                                                                                             \
+            const int o = wv::med3((int)pr + (int)rr, 0, 255);                                                    \
             if (mine) {                                                                                           \
               wv::lds_st8(stS + offT, (unsigned)o);                                                               \
               if ((T) < 2) wv::lds_st8(aS1 + offE, (unsigned)o);                                                  \
@@ -2272,8 +2279,7 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
             enN.y = wv::lds_u32(entS + (int)mN);                                                                  \
             rrN = (unsigned)wv::lds_i16(resS + 32 * (4 * byN + bxN));                                             \
           }                                                                                                       \
-          /* (wave-uniform: the mode pre-pass marked the rounds in which some block of the step takes its own DC) */ \
-          if (dcRounds & (1u << (T))) I4_BODY(T, true) else I4_BODY(T, false)                                     \
+          I4_BODY(T)                                                                                              \
           en = enN;                                                                                               \
           rr = rrN;                                                                                               \
           wv::wave_sync();                                                                                        \
@@ -2281,6 +2287,7 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
         I4_STEP(0) I4_STEP(1) I4_STEP(2) I4_STEP(3) I4_STEP(4) I4_STEP(5) I4_STEP(6) I4_STEP(7) I4_STEP(8) I4_STEP(9)
 #undef I4_STEP
 #undef I4_BODY
+#undef I4_DCV
       }
       }
 
@@ -2296,16 +2303,17 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
 
       // ================= luma write-out ============================================================================
       EXP_REP(11) {
-        // bottom line for the row below (ring) or the band below (write-through): lanes 0..3 of row g
-        unsigned v = 0;
-        if (i < 4) v = wv::lds_u32(tile + TILE_STRIDE * 16 + 8 + 16 * slot + 4 * i);
-        if (valid && i < 4 && g < 3 && g < gl) wv::lds_st32(ringy(ts, g + 1, x, par) + 4 * i, v);
-        if (hasBelow && wv::any(valid && g == gl)) {
+        // bottom line for the row below (ring) or the band below (write-through): lanes 0..3 of row g (every lane reads a
+        // dword of the line: no lane mask around the load)
+        const unsigned v = wv::lds_u32(tile + TILE_STRIDE * 16 + 8 + 16 * slot + 4 * (i & 3));
+        if (valid && i < 4 && g < gl) wv::lds_st32(ringy(ts, g + 1, x, par) + 4 * i, v);
+        // (the last row's x is wave-uniform: a scalar test)
+        if (hasBelow && (unsigned)(s - 2 * gl) < (unsigned)W) {
           // the band's last row: a granule {4 pixels, tag} per lane into the hand-off record (lanes 0..3 of the row), each ONE
           // aligned 8-byte write-through store (MI355X_MICROARCH.md / cdna_hip_programming.md Guideline 16, R2: the data is
           // the flag). The tag travels with the pixels: the band below needs no progress word, and this wave no wait for its
           // stores.
-          if (valid && g == gl && i < 4)
+          if (i < 4 && g == gl)
             wv::st_sc1_64((unsigned long long*)handMy + ((HAND_WORDS / 2) * x + i), (unsigned long long)v | ((unsigned long long)A.gen << 32));
         }
       }
@@ -2321,27 +2329,34 @@ WV void band_back(const KParams& P, const Args& A, const int ldsBase, const int 
       }
       wv::wave_sync();
       // flush the staged rows: every NSY-th macroblock, or at the end of a row: 16 * NSY contiguous bytes per pixel row.
+      // All of the decision is scalar. Row fg is at x = s - 2 fg, so a staging group ends (x = NSY - 1 mod NSY) on odd steps
+      // only, and there in the rows fg = k0 mod NSY / 2 alone: two candidates at NSY = 4, each flushed by all lanes with no
+      // lane mask. The end of a row whose width is no multiple of NSY is a path of its own, taken in the last steps of a task.
       EXP_REP(5)
-      // (scalar pre-test: a row flushes at x = NSY - 1 mod NSY or x = W - 1, and every row's x has the parity of s)
-      if (!EXP_SKIP(5) && ((s & 1) != 0 || ((W - 1 - s) & 1) == 0)) {
-        constexpr int LR = 16 * NSY;  // lanes per macroblock row: 16 pixel rows x NSY segments of 16 bytes
+      if (!EXP_SKIP(5)) {
+        auto flush_row = [&](int fg, int xp, int room, bool whole) {
 #pragma unroll
-        for (int it = 0; it < NSY; it++) {
-          // (64 lanes or more per macroblock row: the row and whether it is flushed at all are wave-uniform)
-          const int fg = LR >= 64 ? (64 * it) / LR : (64 / LR) * it + lane / LR;
-          const int w = LR >= 64 ? ((64 * it) % LR) + lane : lane % LR;
-          const int fx = s - 2 * fg, xp = fx & ~(NSY - 1);
-          const bool rowFlush = fg < nR && fx >= 0 && fx < W && ((fx & (NSY - 1)) == NSY - 1 || fx == W - 1);
-          if (LR >= 64 && !rowFlush) continue;
-          const int fy = (w / NSY) & 15, seg = w % NSY;
-          const bool ok = rowFlush && xp + seg <= fx;
-          const int src = ts + S_TILE + TILE_BYTES * (NP * fg + (seg >> 1)) + TILE_STRIDE * (fy + 1) + 8 + 16 * (seg & 1);
-          const u32x2 lo = wv::lds_u64(src), hi = wv::lds_u64(src + 8);
-          // (the lane's part of the address -- its pixel row and segment -- is a constant of the kernel when a macroblock row
-          // takes the whole wave: flushLane; the row's part is wave-uniform)
-          const unsigned off = LR == 64 ? flushLane + (unsigned)(16 * (r0 + fg) * pitchY + 16 * xp)
-                                        : (unsigned)((16 * (r0 + fg) + fy) * pitchY + 16 * (xp + seg));
-          if (ok) wv::st_g128(planeY + off, u32x4{lo.x, lo.y, hi.x, hi.y});
+          for (int pass = 0; pass < FPASSES; pass++) {
+            const int seg = lane % NSY;
+            const bool ok = (FLR >= 64 || lane < FLR) && (whole || seg <= room);
+            const int src = flushSrc + TILE_BYTES * NP * fg + TILE_STRIDE * (64 / NSY) * pass;
+            const u32x2 lo = wv::lds_u64(src), hi = wv::lds_u64(src + 8);
+            const unsigned off = flushLane + (unsigned)((16 * (r0 + fg) + (64 / NSY) * pass) * pitchY + 16 * xp);
+            if (ok) wv::st_g128(planeY + off, u32x4{lo.x, lo.y, hi.x, hi.y});
+          }
+        };
+        if ((s & 1) != 0) {
+          constexpr int STRIDE = NSY / 2 < 4 ? NSY / 2 : 4, ROWS = 4 / STRIDE;
+          const int k0 = ((s - (NSY - 1)) >> 1) & (STRIDE - 1);
+#pragma unroll
+          for (int j = 0; j < ROWS; j++) {
+            const int fg = k0 + STRIDE * j, fx = s - 2 * fg;
+            if (fg < nR && (unsigned)fx < (unsigned)W) flush_row(fg, fx - (NSY - 1), NSY - 1, true);
+          }
+        }
+        if (s >= W - 1 && (W & (NSY - 1)) != 0) {
+          const int e = s - (W - 1);   // row e / 2 is at its last macroblock
+          if ((e & 1) == 0 && (e >> 1) < nR) flush_row(e >> 1, (W - 1) & ~(NSY - 1), (W - 1) & (NSY - 1), false);
         }
       }
       wv::wave_sync();

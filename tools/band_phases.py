@@ -3,7 +3,7 @@
 
 Builds libdryv_recon_bprof.so with -DDRYV_BAND_PROFILE (s_memtime stamps around each phase of the band kernel's step,
 summed per wave into a buffer of their own), runs the C2 workload with the given numbers of frames and prints cycles
-per step and phase. The stamps drain the LDS queue and fence overlaps the real kernel has: read shares, not run time
+per step and phase (--prebuilt LIB: runs a profile library that was built elsewhere instead of compiling one). The stamps drain the LDS queue and fence overlaps the real kernel has: read shares, not run time
 (cdna_hip_programming.md section 7). Never used by tests, bench or the product.
 """
 import ctypes as C
@@ -29,16 +29,27 @@ PHASES = {
 }
 
 
+def build_profile_library(so=None):
+    """The whole library (the loader wants every entry point), its band kernel with the phase stamps."""
+    so = so or os.path.join(_build.LIB, "libdryv_recon_bprof.so")
+    srcs = [os.path.join(_build.CSRC, f) for f in ("recon_band.hip", "output_pack.hip", "deblock.hip", "recon_api.hip",
+                                                   "inter.hip", "inter_bi.hip", "deblock_bs.hip", "inter_deblock.hip", "inter_api.hip")]
+    subprocess.check_call([_build.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
+                           "-DDRYV_BAND_PROFILE", "-o", so] + srcs)
+    return so
+
+
 def main():
     wl = "C2_1080p_intra_4x4"
     args = sys.argv[1:]
     if args and args[0].startswith("C"):
         wl, args = args[0], args[1:]
+    so = None
+    if args and args[0] == "--prebuilt":
+        so, args = args[1], args[2:]
     frame_list = [int(a) for a in args] or [1, 300]
-    so = os.path.join(_build.LIB, "libdryv_recon_bprof.so")
-    srcs = [os.path.join(_build.CSRC, f) for f in ("recon_band.hip", "output_pack.hip", "deblock.hip", "recon_api.hip")]
-    subprocess.check_call([_build.HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared",
-                           "-DDRYV_BAND_PROFILE", "-o", so] + srcs)
+    if so is None:
+        so = build_profile_library()
     import torch
     lib = abi.load_library(so)
     lib.dryv_recon_debug_band_phases.restype = C.c_int
